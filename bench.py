@@ -15,6 +15,16 @@ exact A*), then every timestep's K4 assign -> K2 step -> record on the device. T
 wall time of the K timed steps. N > 1: the planning step does not shard (sequential agent order,
 SURVEY.md §8e), so each rank plans its own replica (seed + rank) — weak scaling.
 
+A plain run (no --full) does only what the headline needs: set up, warm up, time the K steps, write
+--dump-outputs, print the line (its `roofline` and `kernel_stats` come from the timed steps' own
+counters and cost no run). --dump-outputs DIR writes the last timed plan of rank 0 — what the caller
+of plan_mapd_arrays received — as DIR/x.npy, DIR/y.npy, DIR/state.npy (float32, agents x timesteps);
+the instance is seeded, so two builds run with the same arguments are compared array for array.
+
+--full adds the legs that take GPU or CPU runs of their own: `latency` (the round-floor probe), `bfs`,
+`cpu_baseline` (with its same-sample GPU plan) and, with --sharded-k3, `sharded_plan`. The --no-* and
+--bfs-* / --cpu-steps options select among those legs, so they only matter with --full.
+
 Extra objects on the line:
   roofline      the kernel class with the most device time inside the timed steps (HIP events
                 on the library's stream, tsw_get_stats), algorithmic bytes per launch, and the
@@ -62,6 +72,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: latency probe, K1 BFS, CPU baseline, and "
+                         "(--sharded-k3) the sharded plan; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed plan (rank 0) as DIR/x.npy, DIR/y.npy, DIR/state.npy (float32)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-bfs", action="store_true", help="skip the K1 BFS measurement")
     ap.add_argument("--no-plan", action="store_true", help="skip the planning leg (profiling K1 alone)")
@@ -82,7 +97,21 @@ def parse():
                     help="next-hop resolution policy (TSW_F_EAGER_NEXTHOP / TSW_F_LAZY_NEXTHOP)")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL over xGMI, default) or gloo (rehearsing N ranks on one GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.sharded_k3 and not args.full:
+        ap.error("--sharded-k3 is a leg of --full")
+    if args.no_plan and not args.full:
+        ap.error("--no-plan leaves only the K1 BFS leg, which needs --full")
+    return args
+
+
+def dump_outputs(d: str, rec: np.ndarray) -> None:
+    """The last timed plan as its caller received it (rec (n, T) packed x | y<<16 | state<<32), one
+    float32 array per field: small integers, exact in float32 (C3: 3 x 8 MB)."""
+    os.makedirs(d, exist_ok=True)
+    rec = rec.astype(np.uint64)
+    for name, shift, mask in (("x", 0, 0xFFFF), ("y", 16, 0xFFFF), ("state", 32, 0xFF)):
+        np.save(os.path.join(d, name + ".npy"), ((rec >> np.uint64(shift)) & np.uint64(mask)).astype(np.float32))
 
 
 def running_build_id(diag: bool = False):
@@ -393,11 +422,13 @@ def main():
         st = planner.stats()
         dt_max = allmax(dt)
         value = allsum(float(agent_steps)) / dt_max
-        # latency floors of k_plan's round shapes on its own workgroup size (tsw_probe.hip), measured
-        # after the timed region
-        us_wave, us_pass = planner.probe_round_floors(0)
+        if rank == 0 and args.dump_outputs and last_rec is not None:
+            dump_outputs(args.dump_outputs, last_rec)
+        # --full: latency floors of k_plan's round shapes on its own workgroup size (tsw_probe.hip),
+        # measured after the timed region
+        us_wave, us_pass = planner.probe_round_floors(0) if args.full else (None, None)
         gpu_prefix = None
-        if rank == 0 and not args.no_cpu:
+        if rank == 0 and args.full and not args.no_cpu:
             # the CPU baseline's sample on the GPU (outside the timed region)
             planner.clear_tables()
             torch.cuda.synchronize()
@@ -464,15 +495,15 @@ def main():
         roofline["traffic_split"] = (traffic_split(args.config, traffic, n_agents * steps_total / plans,
                                                    st["astar_queries"] / plans, build)
                                      if dom == "k_plan" and not args.exit_mode else None)
-        latency = latency_roofline(st, us_wave, us_pass)
+        latency = latency_roofline(st, us_wave, us_pass) if args.full else None
 
     sharded = None
-    if world > 1 and not args.no_plan and args.sharded_k3:
+    if world > 1 and not args.no_plan and args.full and args.sharded_k3:
         sharded = sharded_plan_leg(args, rank, world, dev, dist, barrier, allmax)
 
     # K1 BFS alone, den520d-like, 10k distinct goals (configs[3]); rank-local shard of the goals
     bfs = None
-    if not args.no_bfs:
+    if args.full and not args.no_bfs:
         crow = maps.cave_map(256, 257, 0x520D)
         ccells = maps.rows_to_array(crow).reshape(-1)
         free = np.flatnonzero(ccells != ord("@")).astype(np.uint32)
@@ -555,7 +586,7 @@ def main():
         cp.close()
 
     cpu = None
-    if rank == 0 and not args.no_cpu and not args.no_plan:
+    if rank == 0 and args.full and not args.no_cpu and not args.no_plan:
         cpu = cpu_baseline(rows, starts, tasks, n_agents, args.cpu_steps, last_rec, gpu_prefix)
 
     if rank == 0:
@@ -566,7 +597,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(dt_max / args.steps * 1e3, 3) if dt_max is not None else None,
+            "ms_per_step": round(dt_max / args.steps * 1e3, 3) if dt_max is not None and args.steps else None,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

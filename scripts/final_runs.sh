@@ -6,7 +6,7 @@ set -o pipefail
 O=gpurun_out/final
 mkdir -p $O
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 &&
-timeout -k 10 300 python bench.py > $O/bench_driver_style.json 2> $O/bench_driver_style.err &&
+timeout -k 10 300 python bench.py --full > $O/bench_driver_style.json 2> $O/bench_driver_style.err &&
 timeout -k 10 420 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/gpu_tests.log 2>&1 &&
 timeout -k 10 200 python -u scripts/scale_bench.py c3 --cpu-steps 101 > $O/scale_c3.jsonl 2> $O/scale_c3.err &&
 timeout -k 10 200 python -u scripts/scale_bench.py wh10k --cpu-steps 11 > $O/scale_wh10k.jsonl 2> $O/scale_wh10k.err &&

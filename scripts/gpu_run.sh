@@ -43,7 +43,7 @@ for step in "$@"; do
     bfs) run 300 python scripts/bfs_bench.py 10000 5 cave > gpurun_out/bfs_bench.log 2>&1 &&
          run 300 python scripts/bfs_bench.py 2048 3 sort >> gpurun_out/bfs_bench.log 2>&1 || exit $? ;;
     rehearse2) run 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu --dist-backend gloo \
+        --master-port 29533 bench.py --gpus 2 --steps 2 --warmup 1 --full --no-cpu --dist-backend gloo \
         > gpurun_out/rehearse2.json 2> gpurun_out/rehearse2.log || exit $? ;;
     bfsocc) bash scripts/bfs_occ_probe.sh || exit $? ;;
     abplan) bash scripts/ab_plan.sh "TSW_X=0" || exit $? ;;

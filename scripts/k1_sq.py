@@ -1,6 +1,6 @@
 """K1 instruction counts per goal and per BFS level ("put SQ_INSTS_* per level into the
 K1 model"). Input: a `rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVES
-SQ_WAVE_CYCLES -d DIR -- python3 bench.py --no-plan --no-cpu --bfs-reps 2` directory. Every k_bfs_blk
+SQ_WAVE_CYCLES -d DIR -- python3 bench.py --full --no-plan --no-cpu --bfs-reps 2` directory. Every k_bfs_blk
 dispatch of 10,000 den520d goals is summarised; `levels` is the mean BFS depth per goal (372.5 on this
 map, measured with TSW_BFS_PROF in round 2 — the eccentricity of the goals, a property of the map).
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Profiles the default bench on one MI355X (run through gpurun from the repo root).
-#   1. bench.py, the driver's default command                      -> $OUT/bench.json
+#   1. bench.py --full, every leg of the bench line                -> $OUT/bench.json
 #   2. per workload (plan = the C3 planning leg, plan_exit = the same plan in exit mode — the planner's
 #      k_plan dispatches alone, K3 as host-launched passes, for the planner / worker traffic split —
 #      bfs = K1 on den520d, 10k goals), each its own
@@ -14,10 +14,10 @@ TAG=${1:-r5}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-PLAN="--steps 1 --warmup 0 --no-cpu --no-bfs"
-PLANX="--steps 1 --warmup 0 --no-cpu --no-bfs --exit-mode"
-BFS="--no-plan --no-cpu --bfs-reps 2"
-timeout -k 10 300 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err &&
+PLAN="--full --steps 1 --warmup 0 --no-cpu --no-bfs"
+PLANX="--full --steps 1 --warmup 0 --no-cpu --no-bfs --exit-mode"
+BFS="--full --no-plan --no-cpu --bfs-reps 2"
+timeout -k 10 300 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err &&
 for WL in plan plan_exit bfs; do
   if [ $WL = plan ]; then A=$PLAN; elif [ $WL = plan_exit ]; then A=$PLANX; else A=$BFS; fi
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${WL}_trace -o run -- python3 bench.py $A > $OUT/${WL}_trace.json 2> $OUT/${WL}_trace.err &&
