@@ -62,8 +62,10 @@ extern "C" {
  * built against an older header can refuse to run. 3: tsw_opts grew to 24 bytes (watchdog_ms),
  * tsw_next_hop_tables_device gained dev_dist; 4: tsw_abi_version, lazy task-cell checks,
  * tsw_plan_mapd_resolved / tsw_next_hop_codes; 5: tsw_build_id, entry points refuse re-entry from a
- * tsw_plan_mapd_resolved resolver (TSW_EINVAL). */
-#define TSW_ABI_VERSION 6
+ * tsw_plan_mapd_resolved resolver (TSW_EINVAL); 6: tsw_stats coop_worker_queries / coop_worker_pops;
+ * 7: tsw_opts.reserved became host_astar, tsw_stats gained host_astar_queries / host_astar_used /
+ * host_astar_ms, tsw_host_next_hop_codes. */
+#define TSW_ABI_VERSION 7
 
 /* AgentState discriminants in declaration order (src/map/agent.rs:9-15) */
 #define TSW_PICKING 0
@@ -104,8 +106,13 @@ typedef struct {
                                     (0 = half of the device's free memory at tsw_create)            */
     uint32_t watchdog_ms;        /* plan calls: if the planner records no timestep for this long,
                                     the call finishes in exit mode (0 = 10000)                      */
-    uint32_t reserved;
+    uint32_t host_astar;         /* coop mode: host threads answering the planner's needed A* pairs
+                                    during the plan dispatch, the calling thread included (0 = 1;
+                                    TSW_HOST_ASTAR_OFF = none; at most 16)                          */
 } tsw_opts;
+
+/* tsw_opts.host_astar: no host A* service (the K3 workers alone answer the planner). */
+#define TSW_HOST_ASTAR_OFF 0xFFFFFFFFu
 
 /* Resolve every multi-candidate next hop of every table eagerly (one big
  * batched A* pass right after the BFS tables) instead of lazily per step.
@@ -175,6 +182,13 @@ int tsw_plan_mapd_resolved(tsw_ctx *ctx, const tsw_point *starts, uint32_t n, co
  * goals get their K1 table, unresolved cells the exact A*, and both persist for later calls (a
  * goal owner's shard of the next-hop cache). */
 int tsw_next_hop_codes(tsw_ctx *ctx, const uint32_t *start, const uint32_t *goal, uint32_t k, uint8_t *code);
+
+/* The same codes from the host's exact A* alone — no context and no device: cells as tsw_create's
+ * (h rows of w bytes), start[i] / goal[i] free cell ids (TSW_EINVAL otherwise). This is the search the
+ * plan dispatch's host service runs (tsw_opts.host_astar): the BinaryHeap order, the S,E,N,W neighbour
+ * order and the unreachable-goal fallback of get_path, so every code equals the device's. */
+int tsw_host_next_hop_codes(const uint8_t *cells, uint32_t w, uint32_t h, const uint32_t *start,
+                            const uint32_t *goal, uint32_t k, uint8_t *code);
 
 /* Replaces one `tswap_step(&mut agents, &nodes)` call (tswap.rs:174-286;
  * per-tick copy in bin/centralized/manager.rs:147-259 via plan_all_paths
@@ -289,6 +303,11 @@ typedef struct {
      * coop_worker_busy_ms): busy / pops = the in-dispatch time per pop */
     uint64_t coop_worker_queries[3];
     uint64_t coop_worker_pops[3];
+    /* coop mode (ABI 7), host A* service: needed pairs the host answered, codes the planner took from
+     * a host reply (the others arrived from a K3 worker first), and the host's time inside the A* */
+    uint64_t host_astar_queries;
+    uint64_t host_astar_used;
+    double host_astar_ms;
 } tsw_stats;
 int tsw_get_stats(const tsw_ctx *ctx, tsw_stats *out);
 int tsw_reset_stats(tsw_ctx *ctx);

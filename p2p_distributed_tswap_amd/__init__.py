@@ -35,7 +35,8 @@ LIB_PATH = os.path.join(_HERE, "libtswap_hip.so")
 DIAG_LIB_PATH = os.path.join(_HERE, "libtswap_hip_diag.so")
 
 TSW_OK, TSW_EINVAL, TSW_ENOMEM, TSW_EHIP, TSW_EOVERFLOW = 0, -22, -12, -5, -75
-TSW_ABI_VERSION = 6  # include/tswap.h
+TSW_ABI_VERSION = 7  # include/tswap.h
+TSW_HOST_ASTAR_OFF = 0xFFFFFFFF  # tsw_opts.host_astar: no host A* service
 TSW_F_EAGER_NEXTHOP, TSW_F_LAZY_NEXTHOP, TSW_F_EXIT_MODE = 1, 2, 4
 # TswapAction (bin/decentralized/agent.rs:321-326), include/tswap.h TSW_ACT_*
 TSW_ACT_MOVE, TSW_ACT_GOAL_SWAP, TSW_ACT_ROTATION, TSW_ACT_WAIT = 0, 1, 2, 3
@@ -81,7 +82,7 @@ class _Rec(ctypes.Structure):
 class _Opts(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("flags", ctypes.c_uint32),
                 ("table_budget_bytes", ctypes.c_uint64), ("watchdog_ms", ctypes.c_uint32),
-                ("reserved", ctypes.c_uint32)]
+                ("host_astar", ctypes.c_uint32)]
 
 
 class Stats(ctypes.Structure):
@@ -100,6 +101,8 @@ class Stats(ctypes.Structure):
         ("coop_workers", ctypes.c_uint32), ("coop_worker_busy_ms", ctypes.c_double * 3),
         ("watchdog_fires", ctypes.c_uint64), ("tableless_goals", ctypes.c_uint64),
         ("coop_worker_queries", ctypes.c_uint64 * 3), ("coop_worker_pops", ctypes.c_uint64 * 3),
+        ("host_astar_queries", ctypes.c_uint64), ("host_astar_used", ctypes.c_uint64),
+        ("host_astar_ms", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -121,6 +124,7 @@ EXPORTED_SYMBOLS = (
     "tsw_import_tables_device", "tsw_next_hop_tables", "tsw_next_hop_tables_device", "tsw_import_next_hops_device",
     "tsw_clear_tables", "tsw_get_stats", "tsw_reset_stats", "tsw_set_timing", "tsw_probe_round_floors",
     "tsw_abi_version", "tsw_plan_mapd_resolved", "tsw_next_hop_codes", "tsw_build_id",
+    "tsw_host_next_hop_codes",
 )
 
 # tsw_resolve_fn (include/tswap.h): int (*)(void *user, uint32_t k, const uint32_t *start,
@@ -178,6 +182,7 @@ def load_library(path: str = LIB_PATH):
                                            _RESOLVE_FN, vp]
     lib.tsw_plan_mapd_resolved.restype = ctypes.c_int
     lib.tsw_next_hop_codes.argtypes = [vp, P(u32), P(u32), u32, P(ctypes.c_uint8)]
+    lib.tsw_host_next_hop_codes.argtypes = [P(ctypes.c_uint8), u32, u32, P(u32), P(u32), u32, P(ctypes.c_uint8)]
     lib.tsw_next_hop_codes.restype = ctypes.c_int
     lib.tsw_build_id.argtypes = []
     lib.tsw_build_id.restype = ctypes.c_uint64
@@ -217,17 +222,35 @@ def _u32p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
 
 
+def host_next_hop_codes(grid, start, goal) -> np.ndarray:
+    """tsw_host_next_hop_codes: the next-hop codes of get_path(start[i], goal[i]) from the host's exact
+    A* (the plan dispatch's host service) — no context, no device."""
+    lib = load_library(LIB_PATH)
+    cells, w, h = grid_to_bytes(grid)
+    st = np.ascontiguousarray(start, dtype=np.uint32)
+    gl = np.ascontiguousarray(goal, dtype=np.uint32)
+    if st.shape != gl.shape:
+        raise TswapError(TSW_EINVAL, "start and goal must have the same length")
+    out = np.zeros(st.size, dtype=np.uint8)
+    rc = lib.tsw_host_next_hop_codes(cells.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), w, h, _u32p(st), _u32p(gl),
+                                     st.size, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if rc != TSW_OK:
+        raise TswapError(rc, "tsw_host_next_hop_codes: bad grid, or a start / goal that is not a free cell")
+    return out
+
+
 class Planner:
     """One device context (tsw_ctx) bound to a grid."""
 
     def __init__(self, grid, device: int = 0, flags: int = 0, table_budget_bytes: int = 0, watchdog_ms: int = 0,
-                 diag: bool = False):
-        """flags: TSW_F_*; watchdog_ms: tsw_opts.watchdog_ms (0 = 10 s); diag: bind the diagnostic
+                 diag: bool = False, host_astar: int = 0):
+        """flags: TSW_F_*; watchdog_ms: tsw_opts.watchdog_ms (0 = 10 s); host_astar: tsw_opts.host_astar
+        (0 = default, TSW_HOST_ASTAR_OFF = no host A* service, else host threads); diag: bind the diagnostic
         build (reads the TSW_* environment knobs at creation) instead of the production library."""
         self._lib = load_library(DIAG_LIB_PATH if diag else LIB_PATH)
         cells, w, h = grid_to_bytes(grid)
         self.w, self.h = int(w), int(h)
-        opts = _Opts(device, flags, table_budget_bytes, watchdog_ms, 0)
+        opts = _Opts(device, flags, table_budget_bytes, watchdog_ms, host_astar)
         ptr = self._lib.tsw_create(cells.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), w, h,
                                    ctypes.byref(opts))
         if not ptr:

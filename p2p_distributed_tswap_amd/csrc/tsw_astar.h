@@ -3,14 +3,22 @@
 // Rust std BinaryHeap semantics restated (push = sift_up; pop = swap last into the root,
 // sift_down_to_bottom, sift_up), ordered by AstarNode::cmp (tswap.rs:314-321). gfx950 only.
 #pragma once
+// The BinaryHeap order (heap_sift_up / heap_pop) and astar_one are __host__ __device__: the host A*
+// service (tsw_host_astar.cpp, plain C++) runs the same functions over the host copy of the grid, so
+// the heap order lives in one place. Everything wave-level below them is device only.
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define TSW_HD __host__ __device__ __forceinline__
+#else
+#define TSW_HD inline
+#endif
 
 #include "tsw_internal.h"
 
 namespace tsw {
 
 // neighbour directions S,E,N,W = (0,+1),(+1,0),(0,-1),(-1,0): tswap.rs:62
-__device__ __forceinline__ uint32_t step_cell(uint32_t c, uint32_t code, uint32_t W) {
+TSW_HD uint32_t step_cell(uint32_t c, uint32_t code, uint32_t W) {
   switch (code) {
     case 0: return c + W;
     case 1: return c + 1;
@@ -23,7 +31,7 @@ __device__ __forceinline__ uint32_t step_cell(uint32_t c, uint32_t code, uint32_
 // Unreachable-goal fallback of get_path (tswap.rs:378-389): the first
 // neighbour (S,E,N,W order) strictly closer in Manhattan distance; every
 // improving neighbour is exactly 1 closer, so "first improving" == argmin.
-__device__ __forceinline__ uint8_t fallback_code(uint8_t m, uint32_t x, uint32_t y, uint32_t gx,
+TSW_HD uint8_t fallback_code(uint8_t m, uint32_t x, uint32_t y, uint32_t gx,
                                                  uint32_t gy) {
   if ((m & 1) && gy > y) return 0;
   if ((m & 2) && gx > x) return 1;
@@ -32,6 +40,7 @@ __device__ __forceinline__ uint8_t fallback_code(uint8_t m, uint32_t x, uint32_t
   return NH_STAY;
 }
 
+#if defined(__HIPCC__)
 // Next-hop classification from a distance table (any address space).
 __device__ __forceinline__ uint8_t classify_cell(const uint16_t* D, uint32_t c, uint8_t m,
                                                  uint32_t W, uint32_t goal, uint32_t gx,
@@ -61,6 +70,8 @@ __device__ __forceinline__ uint32_t fast_div(uint32_t a, uint32_t b, float inv) 
   return q;
 }
 
+#endif  // __HIPCC__
+
 // ----------------------------------------------------------------------------
 // K3: exact A* next hop, one query per lane.
 // Heap entry: f:21 | g:21 | x:11 | y:11; Rust "a <= b" == key(a) >= key(b).
@@ -71,13 +82,13 @@ __device__ __forceinline__ uint32_t fast_div(uint32_t a, uint32_t b, float inv) 
 // popped, and stale pops relax nothing, so label(goal) at the goal's pop ==
 // the direction of path[1] of the reference's came_from chain (tswap.rs:344-355).
 // ----------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mk_entry(uint32_t f, uint32_t g, uint32_t x, uint32_t y) {
+TSW_HD uint64_t mk_entry(uint32_t f, uint32_t g, uint32_t x, uint32_t y) {
   return ((uint64_t)f << 43) | ((uint64_t)g << 22) | ((uint64_t)x << 11) | (uint64_t)y;
 }
-__device__ __forceinline__ uint64_t ekey(uint64_t e) { return e >> KEY_SHIFT; }
+TSW_HD uint64_t ekey(uint64_t e) { return e >> KEY_SHIFT; }
 
 // BinaryHeap::sift_up(start = 0, pos) with `elem` in the hole.
-__device__ __forceinline__ void heap_sift_up(uint64_t* Hp, uint32_t pos, uint64_t elem) {
+TSW_HD void heap_sift_up(uint64_t* Hp, uint32_t pos, uint64_t elem) {
   const uint64_t k = ekey(elem);
   while (pos > 0) {
     const uint32_t parent = (pos - 1u) >> 1;
@@ -90,7 +101,7 @@ __device__ __forceinline__ void heap_sift_up(uint64_t* Hp, uint32_t pos, uint64_
 }
 
 // BinaryHeap::pop with sift_down_to_bottom(0).
-__device__ __forceinline__ uint64_t heap_pop(uint64_t* Hp, uint32_t& len) {
+TSW_HD uint64_t heap_pop(uint64_t* Hp, uint32_t& len) {
   const uint32_t end = --len;
   const uint64_t last = Hp[end];
   if (end == 0) return last;
@@ -117,7 +128,7 @@ __device__ __forceinline__ uint64_t heap_pop(uint64_t* Hp, uint32_t& len) {
 
 // err == nullptr: a heap overflow returns NH_UNKNOWN with *len_out = -2 (caller re-queues the
 // query to a larger heap) instead of raising ERR_HEAP_OVERFLOW.
-__device__ __forceinline__ uint8_t astar_one(const DevGrid& G, uint32_t v, uint32_t goal, uint32_t tag, uint64_t* Hp,
+TSW_HD uint8_t astar_one(const DevGrid& G, uint32_t v, uint32_t goal, uint32_t tag, uint64_t* Hp,
                                              uint32_t hcap, uint32_t* GS, int32_t* len_out, uint32_t* err) {
   const uint32_t W = G.W;
   const uint32_t vx = v % W, vy = v / W, gx = goal % W, gy = goal / W;
@@ -157,7 +168,11 @@ __device__ __forceinline__ uint8_t astar_one(const DevGrid& G, uint32_t v, uint3
         const uint32_t lab = cg == 0 ? d : labc;
         GS[nc] = tagw | (lab << 20) | tg;
         if (len >= hcap) {
+#if defined(__HIP_DEVICE_COMPILE__)
           if (err) atomicOr(err, ERR_HEAP_OVERFLOW);
+#else
+          if (err) *err |= ERR_HEAP_OVERFLOW;  // host: one thread owns err
+#endif
           *len_out = err ? -1 : -2;
           return NH_UNKNOWN;
         }
@@ -171,6 +186,7 @@ __device__ __forceinline__ uint8_t astar_one(const DevGrid& G, uint32_t v, uint3
   return fallback_code(G.nbmask[v], vx, vy, gx, gy);
 }
 
+#if defined(__HIPCC__)
 // ----------------------------------------------------------------------------
 // Single-lane A* core for k_astar_wave. A lone lane is instruction-bound, so the heap entry
 // keeps its ORDER KEY in the high dword: (f << 15 | g) << 32 | x << 16 | y — one 32-bit
@@ -758,5 +774,7 @@ __device__ __forceinline__ uint8_t astar_wave_par(const DevGrid& G, uint32_t v, 
   *len_out = 2;
   return fallback_code(G.nbmask[v], vx, vy, gx, gy);
 }
+
+#endif  // __HIPCC__
 
 }  // namespace tsw

@@ -12,7 +12,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <condition_variable>
+#include <mutex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "tsw_host_astar.h"
 #include "tsw_internal.h"
 #include "tsw_launch.h"
 #include "tsw_plan.h"
@@ -101,6 +105,9 @@ struct Tunables {
   uint32_t slow_poll = 4;         // TSW_SLOW_POLL: log2 of 1 / (fraction of idle workers polling at full rate) (0: all)
   uint32_t slow_mult = 256;       // TSW_SLOW_MULT: the others' poll interval multiplier
   uint64_t worker_idle_us = 5000000;  // TSW_WORKER_IDLE_US: an idle coop worker exits after this long (test knob)
+  int host_astar = -1;            // TSW_HOST_ASTAR: host A* service threads (0: off; -1: tsw_opts.host_astar)
+  uint32_t host_delay_us = 0;     // TSW_HOST_ASTAR_DELAY_US (test knob): the host holds every reply back this long
+  uint32_t host_ring = 0;         // TSW_HOST_ASTAR_RING (test knob): request / reply ring entries (0: HOST_RING_ENTRIES)
 
   static Tunables from_env() {
     Tunables t;
@@ -162,6 +169,9 @@ struct Tunables {
     t.slow_poll = (uint32_t)num("TSW_SLOW_POLL", 0, 8, t.slow_poll);
     t.slow_mult = (uint32_t)num("TSW_SLOW_MULT", 1, 1024, t.slow_mult);
     t.worker_idle_us = (uint64_t)num("TSW_WORKER_IDLE_US", 1, 5000000, (long)t.worker_idle_us);
+    t.host_astar = (int)num("TSW_HOST_ASTAR", 0, 16, -1);
+    t.host_delay_us = (uint32_t)num("TSW_HOST_ASTAR_DELAY_US", 0, 1000000, 0);
+    t.host_ring = (uint32_t)num("TSW_HOST_ASTAR_RING", 8, 1 << 14, 0);
 #endif
     return t;
   }
@@ -267,6 +277,25 @@ struct tsw_ctx {
   uint32_t* d_flags = nullptr;
   uint64_t coop_aborts = 0;
   uint32_t watchdog_ms = 10000;  // tsw_opts.watchdog_ms
+  // host A* service (coop mode): while k_plan runs, the calling thread (and host_threads - 1 parked
+  // helpers) answer the planner's needed pairs from the request ring (PlanArgs::hreq) with the host A*
+  unsigned long long* h_hreq = nullptr;  // pinned, coherent, mapped: hring entries
+  unsigned long long* d_hreq = nullptr;
+  uint32_t* h_hrep = nullptr;            // pinned, coherent, mapped: hring reply words
+  uint32_t* d_hrep = nullptr;
+  uint32_t hring = 0;
+  uint32_t host_threads = 0;  // 0: service off
+  std::vector<HostAstar> host_scratch;  // one per serving thread ([0]: the calling thread)
+  std::atomic<uint64_t> host_queries{0}, host_busy_ns{0};
+  struct HostPool {
+    std::vector<std::thread> th;
+    std::mutex mu;
+    std::condition_variable cv;
+    uint64_t epoch = 0;  // one per dispatch
+    bool quit = false;
+    std::atomic<bool> active{false};
+    std::atomic<int> running{0};
+  } host_pool;
   // tsw_plan_mapd_resolved: the caller resolves the exit batches (exit mode, lazy next hops)
   tsw_resolve_fn resolver = nullptr;
   void* resolver_user = nullptr;
@@ -1477,6 +1506,68 @@ int resolve_queue(tsw_ctx* c, const AstarQuery* Q, uint32_t nq) {
 }
 
 // Drive k_plan until it reports done; each NEED_QUERIES exit runs K3 on the queued pairs.
+// ---- host A* service ------------------------------------------------------------------------
+// The request ring's next entry, if the planner has written it: claim it (the claim count is the tail
+// the planner reads, h_flags[3]), run the exact A* on this core and write seq << 8 | code into the reply
+// slot. Entries are claimed in ticket order by whichever serving thread sees them first. false: nothing
+// to serve. A pair the host cannot answer gets no reply: a K3 worker answers it as before.
+constexpr uint32_t HOST_RING_ENTRIES = 1u << 14;  // a t = 0 burst of every agent fits (C5: 10,000)
+bool host_serve_one(tsw_ctx* c, HostAstar& S) {
+  const uint32_t mask = c->hring - 1u;
+  uint32_t t = __atomic_load_n(&c->h_flags[3], __ATOMIC_RELAXED);
+  const unsigned long long e = __atomic_load_n(&c->h_hreq[t & mask], __ATOMIC_ACQUIRE);
+  if ((uint32_t)(e >> 40) != t + 1u) return false;
+  if (!__atomic_compare_exchange_n(&c->h_flags[3], &t, t + 1u, false, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED)) return true;
+  const uint32_t v = (uint32_t)(e >> 20) & 0xFFFFFu, g = (uint32_t)e & 0xFFFFFu;
+  if (v >= c->G.ncell || g >= c->G.ncell || !(c->h_nbmask[v] & NB_FREE) || !(c->h_nbmask[g] & NB_FREE)) return true;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint8_t code = host_next_hop(S, c->h_nbmask.data(), c->G.W, c->G.H, v, g);
+  c->host_busy_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  c->host_queries++;
+  if (c->tun.host_delay_us) std::this_thread::sleep_for(std::chrono::microseconds(c->tun.host_delay_us));
+  if (code <= NH_STAY) __atomic_store_n(&c->h_hrep[t & mask], ((t + 1u) << 8) | code, __ATOMIC_RELEASE);
+  return true;
+}
+
+// helper thread k (1..host_threads - 1): parked between dispatches, serving while one runs
+void host_helper(tsw_ctx* c, uint32_t k) {
+  auto& hp = c->host_pool;
+  uint64_t seen = 0;
+  for (;;) {
+    {
+      std::unique_lock<std::mutex> lk(hp.mu);
+      hp.cv.wait(lk, [&] { return hp.quit || hp.epoch != seen; });
+      if (hp.quit) return;
+      seen = hp.epoch;
+    }
+    while (hp.active.load(std::memory_order_acquire))
+      if (!host_serve_one(c, c->host_scratch[k])) __builtin_ia32_pause();
+    hp.running.fetch_sub(1, std::memory_order_release);
+  }
+}
+
+void host_service_begin(tsw_ctx* c) {
+  auto& hp = c->host_pool;
+  const uint32_t helpers = c->host_threads - 1u;
+  if (!helpers) return;
+  while (hp.th.size() < helpers) hp.th.emplace_back(host_helper, c, (uint32_t)hp.th.size() + 1u);
+  hp.running.store((int)helpers, std::memory_order_relaxed);
+  hp.active.store(true, std::memory_order_release);
+  {
+    std::lock_guard<std::mutex> lk(hp.mu);
+    ++hp.epoch;
+  }
+  hp.cv.notify_all();
+}
+
+// every helper is parked again when this returns: the rings may be reset for the next dispatch
+void host_service_end(tsw_ctx* c) {
+  auto& hp = c->host_pool;
+  if (!hp.active.load(std::memory_order_relaxed)) return;
+  hp.active.store(false, std::memory_order_release);
+  while (hp.running.load(std::memory_order_acquire) > 0) std::this_thread::yield();
+}
+
 int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
   *c->h_ctl = init;
   HIPCHK(hipMemcpyAsync(c->d_ctl, c->h_ctl, sizeof(PlanCtl), hipMemcpyHostToDevice, c->s));
@@ -1551,6 +1642,11 @@ int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
               W.nworkers, W.wpb, wcfg.gs_lds, wcfg.hcap, wcfg.dag, W.lds_per_wave);
     if (W.nworkers == 0 || wcfg.hcap < 4u) P.coop = 0;  // nothing fits beside the planner: exit mode
   }
+  // host A* service: coop mode only (exit mode has no waits to shorten)
+  const bool serve = P.coop && c->host_threads && c->h_hreq && c->h_hrep;
+  P.hreq = serve ? c->d_hreq : nullptr;
+  P.hrep = serve ? c->d_hrep : nullptr;
+  P.hring = serve ? c->hring : 0u;
   if (c->tun.plan_debug)
     fprintf(stderr, "[k_plan] planner LDS: agents %u part 0x%x flinks %u occ %u mu %u tasks %u (%zu B)\n", P.agents_lds,
             P.part_lds, P.f_lds, P.occ_lds, P.mu_lds, P.tasks_lds,
@@ -1570,7 +1666,11 @@ int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
       hf[0] = 0u;
       hf[1] = 0u;
       hf[2] = 0u;
-      for (int w = 4; w < 40; ++w) hf[w] = 0u;  // barrier breadcrumbs (TSW_PLAN_DEBUG)
+      for (int w = 3; w < 40; ++w) hf[w] = 0u;  // host A* tail [3], barrier breadcrumbs (TSW_PLAN_DEBUG)
+      if (serve) {
+        memset(c->h_hreq, 0, (size_t)c->hring * sizeof(unsigned long long));
+        memset(c->h_hrep, 0, (size_t)c->hring * sizeof(uint32_t));
+      }
     }
     {
       Timer t(c, CAT_WALK);
@@ -1589,10 +1689,24 @@ int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
       volatile uint32_t* hf = c->h_flags;
       uint32_t last = hf[2];
       auto seen = std::chrono::steady_clock::now();
+      // host A* service: this thread serves the request ring between the checks below, which then run
+      // on a 50 us time basis instead of after a 50 us sleep
+      auto next_check = seen;
+      if (serve) host_service_begin(c);
       for (;;) {
+        if (serve) {
+          const bool any = host_serve_one(c, c->host_scratch[0]);
+          if (std::chrono::steady_clock::now() < next_check) {
+            if (!any) __builtin_ia32_pause();
+            continue;
+          }
+        }
         const hipError_t q = hipStreamQuery(c->s);
         if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) HIPCHK(q);
+        if (q != hipErrorNotReady) {
+          if (serve) host_service_end(c);
+          HIPCHK(q);
+        }
         const uint32_t hb = hf[2];
         const auto now = std::chrono::steady_clock::now();
         if (hb != last) {
@@ -1613,13 +1727,18 @@ int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
             fprintf(stderr, "\n[tswap] first mismatch: wave 0 at %u, another at %u\n", hf[4] >> 16, hf[4] & 0xFFFFu);
           }
         }
-        std::this_thread::sleep_for(std::chrono::microseconds(50));
+        if (serve) next_check = std::chrono::steady_clock::now() + std::chrono::microseconds(50);
+        else std::this_thread::sleep_for(std::chrono::microseconds(50));
       }
+      if (serve) host_service_end(c);
     }
     HIPCHK(hipStreamSynchronize(c->s));
     if (coop) {
       HIPCHK(hipMemcpy(c->h_cc, c->d_cc, sizeof(CoopCtl), hipMemcpyDeviceToHost));
       const CoopCtl& cc = *c->h_cc;
+      c->st.host_astar_queries += c->host_queries.exchange(0);
+      c->st.host_astar_ms += (double)c->host_busy_ns.exchange(0) * 1e-6;
+      c->st.host_astar_used += cc.host_used;
       c->st.coop_waits += cc.waits;
       c->st.coop_wait_ms += (double)cc.wait_ticks / (double)c->wall_khz;
       for (int k = 0; k < 8; ++k) {
@@ -1988,6 +2107,12 @@ tsw_ctx* tsw_create(const uint8_t* cells, uint32_t w, uint32_t h, const tsw_opts
   c->flags = opts ? opts->flags : 0;
   if (c->flags & TSW_F_EXIT_MODE) c->tun.coop = false;
   if (opts && opts->watchdog_ms) c->watchdog_ms = opts->watchdog_ms;
+  {
+    // host A* service threads: the measured default is the calling thread alone
+    const uint32_t ha = opts ? opts->host_astar : 0u;
+    c->host_threads = ha == TSW_HOST_ASTAR_OFF ? 0u : ha == 0u ? 1u : std::min<uint32_t>(ha, 16u);
+    if (c->tun.host_astar >= 0) c->host_threads = (uint32_t)c->tun.host_astar;
+  }
   if (c->device < 0 || c->device >= ndev) {
     g_create_err = "tsw_create: bad device ordinal";
     delete c;
@@ -2104,6 +2229,30 @@ tsw_ctx* tsw_create(const uint8_t* cells, uint32_t w, uint32_t h, const tsw_opts
     return fail("pinned flags", e);
   if ((e = hipHostGetDevicePointer((void**)&c->d_flags, c->h_flags, 0)) != hipSuccess)
     return fail("flags device pointer", e);
+  if (c->host_threads) {
+    uint32_t ring = HOST_RING_ENTRIES;
+    if (c->tun.host_ring) {
+      ring = 8u;
+      while (ring * 2u <= c->tun.host_ring) ring *= 2u;
+    }
+    c->hring = ring;
+    if ((e = hipHostMalloc(&c->h_hreq, (size_t)ring * sizeof(unsigned long long), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess)
+      return fail("pinned request ring", e);
+    if ((e = hipHostGetDevicePointer((void**)&c->d_hreq, c->h_hreq, 0)) != hipSuccess) return fail("request ring device pointer", e);
+    if ((e = hipHostMalloc(&c->h_hrep, (size_t)ring * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped)) != hipSuccess)
+      return fail("pinned reply ring", e);
+    if ((e = hipHostGetDevicePointer((void**)&c->d_hrep, c->h_hrep, 0)) != hipSuccess) return fail("reply ring device pointer", e);
+    // the serving threads' scratch is sized here, so nothing allocates (or throws) while a dispatch runs
+    try {
+      c->host_scratch.resize(c->host_threads);
+      for (HostAstar& S : c->host_scratch) {
+        S.gs.assign(ncell, 0u);
+        S.heap.resize(4u * (size_t)ncell + 8u);
+      }
+    } catch (const std::bad_alloc&) {
+      return fail("host A* scratch", hipErrorOutOfMemory);
+    }
+  }
   memset(c->h_stat, 0, sizeof(DevStatus));
   size_t freeb = 0, totalb = 0;
   hipMemGetInfo(&freeb, &totalb);
@@ -2114,6 +2263,15 @@ tsw_ctx* tsw_create(const uint8_t* cells, uint32_t w, uint32_t h, const tsw_opts
 
 void tsw_destroy(tsw_ctx* c) {
   if (!c) return;
+  if (!c->host_pool.th.empty()) {
+    {
+      std::lock_guard<std::mutex> lk(c->host_pool.mu);
+      c->host_pool.quit = true;
+    }
+    c->host_pool.cv.notify_all();
+    for (auto& t : c->host_pool.th) t.join();
+    c->host_pool.th.clear();
+  }
   hipSetDevice(c->device);
   if (c->s) hipStreamSynchronize(c->s);
   auto fre = [](void* p) {
@@ -2130,6 +2288,8 @@ void tsw_destroy(tsw_ctx* c) {
   fre(c->d_cc); fre(c->d_QS); fre(c->d_QT); fre(c->d_QH); fre(c->d_QP); fre(c->d_pred); fre(c->d_wf); fre(c->d_govf); fre(c->d_mg_grp); fre(c->d_mg_wl); fre(c->d_mg_anch);
   if (c->h_cc) (void)hipHostFree(c->h_cc);
   if (c->h_flags) (void)hipHostFree(c->h_flags);
+  if (c->h_hreq) (void)hipHostFree(c->h_hreq);
+  if (c->h_hrep) (void)hipHostFree(c->h_hrep);
   if (c->h_stat) hipHostFree(c->h_stat);
   if (c->h_ctl) hipHostFree(c->h_ctl);
   for (auto& e : c->pending) {

@@ -111,6 +111,7 @@ struct CoopCtl {
   uint32_t dbg_tag[2][64];
   // predicted task chains: jobs run, and (TSW_PLAN_DEBUG) assignments whose task was the agent's last prediction
   uint32_t pred_jobs, pred_asg, pred_hit, pred_none;
+  uint32_t host_asked, host_used;  // host A* service: pairs the planner asked the host for / codes it took from a reply
 };
 
 struct AstarQuery {

@@ -124,9 +124,21 @@ struct PlanArgs {
   uint4* wf;            // per agent: step-start walk-ahead frontier (cell at the walk, goal, stopping cell, its hop); nullptr: off
   CoopCtl* cc;
   // host-visible (pinned, system-coherent) words: [0] set when the planner block is resident,
-  // [1] abort (host watchdog: planner waits give up, workers exit), [2] planner heartbeat (timesteps)
+  // [1] abort (host watchdog: planner waits give up, workers exit), [2] planner heartbeat (timesteps),
+  // [3] host A* service: request-ring entries the host has claimed so far (written by the host)
   uint32_t* hflags;
+  // host A* service (coop mode, tsw_capi.hip serve_host_astar): rings of hring entries (a power of two;
+  // 0 = service off) in mapped coherent host memory. A planner thread waiting for a needed pair takes
+  // ticket t (0, 1, ... per launch) and stores seq << 40 | v << 20 | goal into hreq[t % hring] with
+  // seq = t + 1: one 64-bit system-scope store carries the whole request, so no head word and no
+  // release (an L2 write-back) is needed — the host polls the next slot for its seq. The host answers
+  // with seq << 8 | code in hrep[t % hring]. The planner never waits for the host: a missing, late or
+  // foreign reply is ignored and the code arrives from a K3 worker as before.
+  unsigned long long* hreq;
+  uint32_t* hrep;
+  uint32_t hring;
 };
+constexpr uint32_t HOST_RING_MAX_TICKETS = 0xFFFFF0u;  // seq fits 24 bits (hrep keeps 8 for the code)
 
 // Agent arrays that go to LDS one by one when all of them do not fit (PlanArgs::part_lds), in the
 // order the host admits them: the rules phase's successor chains and labels first (its relabel walks

@@ -499,6 +499,8 @@ enum : int { COOP_OK = 0, COOP_GIVE_UP = 1, COOP_RETRY = 2 };
 // safety limit (the caller exits to the host). COOP_RETRY: a pair stayed pending for 20 ms — more
 // than any A* on these grids; the caller queues the still-pending pairs again (a duplicate query
 // resolves to the same code), so a lost update can cost a retry but never a stall.
+// With the host A* service on (P.hring != 0, PlanArgs::hreq) the pairs waited for are also asked of the
+// host, and a wait ends on whichever answer arrives first; nothing here ever waits for the host.
 __device__ int coop_wait(const PlanArgs& P, const Arrays& S, uint32_t* s_q, uint32_t* s_flag, uint32_t sec) {
   const uint32_t tid = threadIdx.x, bd = blockDim.x;
   if (tid == 0) {
@@ -510,15 +512,70 @@ __device__ int coop_wait(const PlanArgs& P, const Arrays& S, uint32_t* s_q, uint
       P.cc->dbg_depth += dep;
       P.cc->dbg_depth_max = max(P.cc->dbg_depth_max, dep);
     }
+    if (P.hring)
+      s_q[11] = min(__hip_atomic_load(&P.hflags[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) + P.hring,
+                    HOST_RING_MAX_TICKETS);
   }
   PBAR();
   const unsigned long long t0 = wall_clock64();
+  // host A* service: the pairs this thread is about to spin on — its dirty agents whose code reads
+  // pending (queued for the workers) right now — are also asked of the host, when their tickets fit the
+  // ring; the loop below then takes whichever answer comes first. A dirty agent whose code is resolved or
+  // not queued leaves the loop at its first read and is not asked (asking for every dirty agent kept one
+  // host core busy with pairs nobody waited for). hmask: bit j = the thread's j-th dirty agent was asked
+  // (the first 32 of them), its ticket is hbase + the number of asked ones before it.
+  uint32_t hbase = 0, hmask = 0;
+  if (P.hring) {
+    uint32_t j = 0;
+    for (uint32_t k = tid; k < P.n && j < 32u; k += bd) {
+      if (S.NHC[k] <= NH_STAY || S.V[k] == S.G[k] || S.GT[k] < 0) continue;
+      const uint8_t* p = P.nh + (uint64_t)S.GT[k] * P.nstride + S.V[k];
+      const uint8_t c = (uint8_t)(ld_agent(reinterpret_cast<const uint32_t*>((uintptr_t)p & ~(uintptr_t)3u)) >>
+                                  (8u * (uint32_t)((uintptr_t)p & 3u)));
+      if (c == NH_PENDING || c == NH_PENDING_S) hmask |= 1u << j;
+      ++j;
+    }
+    if (hmask) {
+      const uint32_t cnt = (uint32_t)__builtin_popcount(hmask);
+      uint32_t cur = *(volatile uint32_t*)&s_q[10];
+      bool got = false;
+      while (cur + cnt <= s_q[11]) {
+        const uint32_t prev = atomicCAS(&s_q[10], cur, cur + cnt);
+        if (prev == cur) {
+          hbase = cur;
+          got = true;
+          break;
+        }
+        cur = prev;
+      }
+      if (!got) hmask = 0;  // the ring is full: not asked
+    }
+    if (hmask) {
+      uint32_t t = hbase;
+      j = 0;
+      for (uint32_t k = tid; k < P.n && j < 32u; k += bd) {
+        if (S.NHC[k] <= NH_STAY || S.V[k] == S.G[k] || S.GT[k] < 0) continue;
+        if ((hmask >> j) & 1u) {
+          __hip_atomic_store(&P.hreq[t & (P.hring - 1u)],
+                             ((unsigned long long)(t + 1u) << 40) | ((unsigned long long)S.V[k] << 20) | S.G[k],
+                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          ++t;
+        }
+        ++j;
+      }
+      atomicAdd(&P.cc->host_asked, t - hbase);
+    }
+  }
   int st = COOP_OK;
+  uint32_t hj = 0;  // index of the dirty agent at hand among this thread's
   for (uint32_t k = tid; k < P.n && st == COOP_OK; k += bd) {
     if (S.NHC[k] <= NH_STAY) continue;
     const uint32_t v = S.V[k];
     const int32_t tab = S.GT[k];
     if (v == S.G[k] || tab < 0) continue;
+    const bool asked = hj < 32u && ((hmask >> hj) & 1u);
+    const uint32_t tk = hbase + (uint32_t)__builtin_popcount(hmask & ((1u << (hj & 31u)) - 1u));  // its ticket, if asked
+    ++hj;
     const uint8_t* p = P.nh + (uint64_t)tab * P.nstride + v;
     const uint32_t* w = reinterpret_cast<const uint32_t*>((uintptr_t)p & ~(uintptr_t)3u);
     const uint32_t sh = 8u * (uint32_t)((uintptr_t)p & 3u);
@@ -529,6 +586,16 @@ __device__ int coop_wait(const PlanArgs& P, const Arrays& S, uint32_t* s_q, uint
         break;
       }
       if (c == NH_UNKNOWN) break;
+      if (asked) {
+        // the host's reply for this ticket (another seq: an older or no reply): publish the code as a worker does
+        const uint32_t r = __hip_atomic_load(&P.hrep[tk & (P.hring - 1u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if ((r >> 8) == tk + 1u && (r & 0xFFu) <= NH_STAY) {
+          __hip_atomic_store(const_cast<uint8_t*>(p), (uint8_t)(r & 0xFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          S.NHC[k] = (uint8_t)(r & 0xFFu);
+          atomicAdd(&P.cc->host_used, 1u);
+          break;
+        }
+      }
       const unsigned long long dt = wall_clock64() - t0;
       if (dt > COOP_GIVE_UP_TICKS || ld_agent(&P.cc->err) != 0u ||
           (ld_agent(&P.cc->alive) == 0u && wall_clock64() - S.t0 > COOP_NO_WORKER_TICKS) ||
@@ -937,7 +1004,7 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
     return;
   }
   __shared__ PlanCtl s_ctl;
-  __shared__ uint32_t s_q[10], s_need, s_cnt, s_doit, s_px, s_py, s_exit, s_best, s_miss, s_flag, s_abort, s_cabort, s_hops,
+  __shared__ uint32_t s_q[12], s_need, s_cnt, s_doit, s_px, s_py, s_exit, s_best, s_miss, s_flag, s_abort, s_cabort, s_hops,
       s_badat;
   __shared__ uint32_t s_ap[128];  // rules: members of a rule-4 cycle rotated by the wave (<= 64), links
   __shared__ uint32_t s_wcount[16];
@@ -1067,6 +1134,8 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
     s_q[7] = 0;  // ... last published head
     s_q[8] = 0;  // predicted task chains queued this launch (coop mode)
     s_q[9] = 0;  // ... last published head
+    s_q[10] = 0;  // host A* service: request tickets taken this launch
+    s_q[11] = 0;  // ... tickets below this fit the ring (claimed by the host + ring size, read at each wait)
     if (P.coop) __hip_atomic_store(&P.cc->t_now, s_ctl.t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int k = 0; k < 48; ++k) s_tick[k] = 0;
     bar_ids()[16] = 0u;

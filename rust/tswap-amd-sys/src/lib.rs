@@ -35,7 +35,10 @@ pub const TSW_ENODEV: c_int = -19;
 
 /// ABI revision of include/tswap.h this crate mirrors; `Planner::new` refuses a library built
 /// against another one.
-pub const TSW_ABI_VERSION: c_int = 6;
+pub const TSW_ABI_VERSION: c_int = 7;
+
+/// `TswOpts::host_astar`: no host A* service.
+pub const TSW_HOST_ASTAR_OFF: u32 = 0xFFFFFFFF;
 
 pub const TSW_PICKING: u8 = 0;
 pub const TSW_CARRYING: u8 = 1;
@@ -93,7 +96,7 @@ pub struct TswOpts {
     pub flags: u32,
     pub table_budget_bytes: u64,
     pub watchdog_ms: u32,
-    pub reserved: u32,
+    pub host_astar: u32,
 }
 
 #[repr(C)]
@@ -130,6 +133,9 @@ pub struct TswStats {
     pub tableless_goals: u64,
     pub coop_worker_queries: [u64; 3],
     pub coop_worker_pops: [u64; 3],
+    pub host_astar_queries: u64,
+    pub host_astar_used: u64,
+    pub host_astar_ms: f64,
 }
 
 extern "C" {
@@ -140,6 +146,8 @@ extern "C" {
                                   max_t: u32, out: *mut TswRec, goal_out: *mut u32, out_t: *mut u32,
                                   resolve: TswResolveFn, user: *mut c_void) -> c_int;
     pub fn tsw_next_hop_codes(ctx: *mut TswCtx, start: *const u32, goal: *const u32, k: u32, code: *mut u8) -> c_int;
+    pub fn tsw_host_next_hop_codes(cells: *const u8, w: u32, h: u32, start: *const u32, goal: *const u32, k: u32,
+                                   code: *mut u8) -> c_int;
     pub fn tsw_abi_version() -> c_int;
     pub fn tsw_build_id() -> u64;
     pub fn tsw_plan_mapd(ctx: *mut TswCtx, starts: *const TswPoint, n: u32, tasks: *const TswTask, m: u32,
@@ -314,7 +322,7 @@ impl Planner {
             flags: opts.flags,
             table_budget_bytes: opts.table_budget_bytes,
             watchdog_ms: opts.watchdog_ms,
-            reserved: 0,
+            host_astar: 0,
         };
         let ctx = unsafe { tsw_create(cells.as_ptr(), w as u32, h as u32, &o) };
         if ctx.is_null() {
