@@ -32,8 +32,9 @@
  *     a heap past their LDS capacity to the global-heap kernel (20-bit g, enough
  *     for any path on a 2^20-cell grid); its heap holds min(4*cells+8, 65536)
  *     entries, past that TSW_EOVERFLOW
- *   - tsw_decide: at most 1024 entries in one agent's nearby list (TSW_EOVERFLOW;
- *     get_nearby, decentralized/agent.rs:108-153, has no bound)
+ *   - tsw_decide, tsw_decide_fleet: at most 1024 entries in one agent's nearby list (TSW_EOVERFLOW
+ *     when a longer list reaches Rule 4; get_nearby, decentralized/agent.rs:108-153, has no bound)
+ *   - tsw_nearby, tsw_decide_fleet: the lists of one call hold at most 2^32 - 1 entries (TSW_EOVERFLOW)
  *   - goal tables: table_budget_bytes (2 B per cell per goal). Tables not used by
  *     the current call are evicted least-recently-used first; TSW_ENOMEM only
  *     when the goals of ONE call do not fit.
@@ -64,8 +65,8 @@ extern "C" {
  * tsw_plan_mapd_resolved / tsw_next_hop_codes; 5: tsw_build_id, entry points refuse re-entry from a
  * tsw_plan_mapd_resolved resolver (TSW_EINVAL); 6: tsw_stats coop_worker_queries / coop_worker_pops;
  * 7: tsw_opts.reserved became host_astar, tsw_stats gained host_astar_queries / host_astar_used /
- * host_astar_ms, tsw_host_next_hop_codes. */
-#define TSW_ABI_VERSION 7
+ * host_astar_ms, tsw_host_next_hop_codes; 8: tsw_nearby, tsw_decide_fleet. */
+#define TSW_ABI_VERSION 8
 
 /* AgentState discriminants in declaration order (src/map/agent.rs:9-15) */
 #define TSW_PICKING 0
@@ -218,6 +219,32 @@ int tsw_get_path_next(tsw_ctx *ctx, const uint32_t *start, const uint32_t *goal,
 int tsw_decide(tsw_ctx *ctx, const uint32_t *my_v, const uint32_t *my_g, uint32_t n, const uint32_t *nb_off,
                const uint32_t *nb_v, const uint32_t *nb_g, uint32_t *act, uint32_t *cell, uint32_t *partner,
                uint32_t *npart, uint32_t *part);
+
+/* K5: NearbyAgents::get_nearby (agent.rs:108-153) for a whole fleet. v[i] = cell id of agent i
+ * (any on-grid cell; TSW_EINVAL for an id >= w*h). Agent i's list is every agent j != i with
+ * |xi-xj| + |yi-yj| <= radius (obstacles play no part; agents sharing i's cell are included; self is
+ * excluded by index), in ASCENDING AGENT INDEX. The reference's list order is a HashMap iteration
+ * order, i.e. unspecified; ascending agent index is this library's deterministic choice. A decision
+ * depends on the order only through "first entry at a position", which this order makes the
+ * smallest-index agent at the cell. nb_off[n+1] is always written; *total = nb_off[n].
+ * nb_idx (agent indices, CSR) is written only when *total <= cap; otherwise TSW_EOVERFLOW with nb_off
+ * and *total valid (nb_idx may be NULL with cap 0: a size query). n == 0: TSW_OK with nb_off[0] = 0.
+ * Duplicate positions are legal (in the decentralized mode they stand for stale information). */
+int tsw_nearby(tsw_ctx *ctx, const uint32_t *v, uint32_t n, uint32_t radius,
+               uint32_t *nb_off, uint32_t *nb_idx, uint32_t cap, uint32_t *total);
+
+/* One decentralized tick for the fleet: the lists of tsw_nearby, then compute_next_move_with_tswap for
+ * every agent, all on the device (the lists never visit the host). Defined as: the outputs of
+ * tsw_decide(my_v = v, my_g = g, lists nb_v[k] = v[nb_idx[k]], nb_g[k] = g[nb_idx[k]]) with every list
+ * index replaced by the agent index it names. act/cell as tsw_decide; partner[i] = AGENT index or
+ * 0xFFFFFFFF; rotation participants as agent indices in part[part_off[i] .. part_off[i+1]) (empty
+ * unless act[i] == TSW_ACT_ROTATION). part_off[n] > part_cap: TSW_EOVERFLOW with act, cell, partner,
+ * part_off complete and part untouched. Errors as tsw_decide: a v[i] or g[i] off-grid or blocked is
+ * TSW_EINVAL; a list of more than 1024 entries that reaches Rule 4 is TSW_EOVERFLOW (part_off[n] is
+ * then not written). n == 0: TSW_OK with part_off[0] = 0. */
+int tsw_decide_fleet(tsw_ctx *ctx, const uint32_t *v, const uint32_t *g, uint32_t n, uint32_t radius,
+                     uint32_t *act, uint32_t *cell, uint32_t *partner,
+                     uint32_t *part_off, uint32_t *part, uint32_t part_cap);
 
 /* K1: BFS distance tables for k goal cells, u16 per cell, row-major
  * (TSW_DIST_INF for blocked/unreachable). out: host buffer k*w*h. */

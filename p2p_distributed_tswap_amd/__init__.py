@@ -35,7 +35,7 @@ LIB_PATH = os.path.join(_HERE, "libtswap_hip.so")
 DIAG_LIB_PATH = os.path.join(_HERE, "libtswap_hip_diag.so")
 
 TSW_OK, TSW_EINVAL, TSW_ENOMEM, TSW_EHIP, TSW_EOVERFLOW = 0, -22, -12, -5, -75
-TSW_ABI_VERSION = 7  # include/tswap.h
+TSW_ABI_VERSION = 8  # include/tswap.h
 TSW_HOST_ASTAR_OFF = 0xFFFFFFFF  # tsw_opts.host_astar: no host A* service
 TSW_F_EAGER_NEXTHOP, TSW_F_LAZY_NEXTHOP, TSW_F_EXIT_MODE = 1, 2, 4
 # TswapAction (bin/decentralized/agent.rs:321-326), include/tswap.h TSW_ACT_*
@@ -124,7 +124,7 @@ EXPORTED_SYMBOLS = (
     "tsw_import_tables_device", "tsw_next_hop_tables", "tsw_next_hop_tables_device", "tsw_import_next_hops_device",
     "tsw_clear_tables", "tsw_get_stats", "tsw_reset_stats", "tsw_set_timing", "tsw_probe_round_floors",
     "tsw_abi_version", "tsw_plan_mapd_resolved", "tsw_next_hop_codes", "tsw_build_id",
-    "tsw_host_next_hop_codes",
+    "tsw_host_next_hop_codes", "tsw_nearby", "tsw_decide_fleet",
 )
 
 # tsw_resolve_fn (include/tswap.h): int (*)(void *user, uint32_t k, const uint32_t *start,
@@ -167,6 +167,10 @@ def load_library(path: str = LIB_PATH):
     lib.tsw_get_path_next.argtypes = [vp, P(u32), P(u32), u32, P(u32), P(i32)]
     lib.tsw_decide.argtypes = [vp, P(u32), P(u32), u32, P(u32), P(u32), P(u32), P(u32), P(u32), P(u32), P(u32),
                                P(u32)]
+    lib.tsw_nearby.argtypes = [vp, P(u32), u32, u32, P(u32), P(u32), u32, P(u32)]
+    lib.tsw_nearby.restype = ctypes.c_int
+    lib.tsw_decide_fleet.argtypes = [vp, P(u32), P(u32), u32, u32, P(u32), P(u32), P(u32), P(u32), P(u32), u32]
+    lib.tsw_decide_fleet.restype = ctypes.c_int
     lib.tsw_dist_tables.argtypes = [vp, P(u32), u32, P(ctypes.c_uint16)]
     lib.tsw_dist_tables_device.argtypes = [vp, P(u32), u32, vp]
     lib.tsw_import_tables_device.argtypes = [vp, P(u32), u32, vp]
@@ -408,6 +412,49 @@ class Planner:
             b = int(off[i]) + i
             out.append((int(act[i]), int(cell[i]), int(partner[i]), [int(x) for x in part[b:b + npart[i]]]))
         return out
+
+    # --- decentralized mode for a whole fleet (tsw_nearby / tsw_decide_fleet) ---
+    def nearby(self, v, radius: int = 15):
+        """NearbyAgents::get_nearby (agent.rs:108-153) for every agent at once, on the device.
+        v: (n,) cell ids. Returns (nb_off (n+1,), nb_idx): agent i's list is the agent indices
+        nb_idx[nb_off[i]:nb_off[i+1]], every j != i within Manhattan `radius`, ascending."""
+        v = np.ascontiguousarray(v, dtype=np.uint32)
+        n = v.size
+        off = np.zeros(n + 1, dtype=np.uint32)
+        total = ctypes.c_uint32(0)
+        rc = self._lib.tsw_nearby(self._ctx, _u32p(v), n, radius, _u32p(off), None, 0, ctypes.byref(total))  # size query
+        if rc != TSW_EOVERFLOW or total.value == 0:
+            self._check(rc)
+            return off, np.zeros(0, dtype=np.uint32)
+        idx = np.zeros(total.value, dtype=np.uint32)
+        self._check(self._lib.tsw_nearby(self._ctx, _u32p(v), n, radius, _u32p(off), _u32p(idx), idx.size,
+                                         ctypes.byref(total)))
+        return off, idx
+
+    def decide_fleet(self, v, g, radius: int = 15, part_cap: Optional[int] = None):
+        """One decentralized tick for the fleet (tsw_decide_fleet): every agent's nearby list and its
+        compute_next_move_with_tswap decision, on the device. v, g: (n,) cell / goal cell ids.
+        Returns numpy arrays (act, cell, partner, part_off, part): act[i] one of TSW_ACT_*, cell[i] the
+        Move destination, partner[i] the goal-swap partner's AGENT index (0xFFFFFFFF otherwise), and
+        agent i's rotation participants as agent indices part[part_off[i]:part_off[i+1]]."""
+        v = np.ascontiguousarray(v, dtype=np.uint32)
+        g = np.ascontiguousarray(g, dtype=np.uint32)
+        n = v.size
+        if g.size != n:
+            raise TswapError(TSW_EINVAL, "v and g must have the same length")
+        act, cell, partner = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        off = np.zeros(n + 1, dtype=np.uint32)
+        cap = 4 * n + 64 if part_cap is None else int(part_cap)
+        for attempt in range(2):
+            part = np.zeros(cap, dtype=np.uint32)
+            rc = self._lib.tsw_decide_fleet(self._ctx, _u32p(v), _u32p(g), n, radius, _u32p(act), _u32p(cell),
+                                            _u32p(partner), _u32p(off), _u32p(part), cap)
+            # TSW_EOVERFLOW with part_off[n] > cap: part was too small, and part_off[n] is what it takes
+            if rc != TSW_EOVERFLOW or attempt or part_cap is not None or int(off[n]) <= cap:
+                break
+            cap = int(off[n])
+        self._check(rc)
+        return act, cell, partner, off, part[:int(off[n])]
 
     # --- get_path -----------------------------------------------------------
     def get_path_next(self, start: np.ndarray, goal: np.ndarray):

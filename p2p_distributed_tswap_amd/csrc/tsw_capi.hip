@@ -26,6 +26,7 @@
 #include "tsw_host_astar.h"
 #include "tsw_internal.h"
 #include "tsw_launch.h"
+#include "tsw_nearby.h"
 #include "tsw_plan.h"
 #include "tswap.h"
 
@@ -343,6 +344,12 @@ struct tsw_ctx {
   // temporaries
   uint32_t *d_tmp_a = nullptr, *d_tmp_b = nullptr, *d_tmp_c = nullptr;
   size_t tmp_cap = 0;
+  // tsw_nearby / tsw_decide_fleet scratch (grow-only): [0] bins, counts and offsets (sized by the fleet
+  // and the grid), [1] the lists and k_decide's arrays (sized by the lists' total)
+  uint32_t* d_fleet[2] = {nullptr, nullptr};
+  size_t fleet_cap[2] = {0, 0};
+  uint32_t* h_fleet = nullptr;  // pinned staging of tsw_decide_fleet: v | g up, act | cell | partner | part_off down
+  size_t h_fleet_cap = 0;
 
   // stats / timing
   tsw_stats st{};
@@ -656,11 +663,14 @@ int check_err(tsw_ctx* c) {
   e = c->h_stat->err;
   if (e) {
     char buf[160];
-    snprintf(buf, sizeof buf, "device error bits 0x%x (1 heap overflow, 2 dist overflow, 4 g overflow, 8 no table)",
+    snprintf(buf, sizeof buf,
+             "device error bits 0x%x (1 heap overflow, 2 dist overflow, 4 g overflow, 8 no table, 64 nearby list "
+             "of more than 1024 entries)",
              e);
     c->err = buf;
     HIPCHK(hipMemsetAsync(&c->d_stat->err, 0, 4, c->s));
-    return (e & (ERR_HEAP_OVERFLOW | ERR_DIST_OVERFLOW | ERR_G_OVERFLOW)) ? TSW_EOVERFLOW : TSW_EINVAL;
+    // ERR_DECIDE_LIST: the list limit tswap.h documents as TSW_EOVERFLOW
+    return (e & (ERR_HEAP_OVERFLOW | ERR_DIST_OVERFLOW | ERR_G_OVERFLOW | ERR_DECIDE_LIST)) ? TSW_EOVERFLOW : TSW_EINVAL;
   }
   return TSW_OK;
 }
@@ -2284,12 +2294,13 @@ void tsw_destroy(tsw_ctx* c) {
   fre(c->d_gt); fre(c->d_dec); fre(c->d_mu); fre(c->d_dups); fre(c->d_onc); fre(c->d_candc); fre(c->d_f1); fre(c->d_f2);
   if (c->h_dups) (void)hipHostFree(c->h_dups);
   fre(c->d_task); fre(c->d_occ); fre(c->d_nhc); fre(c->d_ctl); fre(c->d_pargs); fre(c->d_ticks); fre(c->d_dtag); fre(c->d_live); fre(c->d_klt); fre(c->d_kpos); fre(c->d_kbox); fre(c->d_kcnt); fre(c->d_pick); fre(c->d_dlv); fre(c->d_unused);
-  fre(c->d_rec); fre(c->d_grec); fre(c->d_tmp_a); fre(c->d_tmp_b);
+  fre(c->d_rec); fre(c->d_grec); fre(c->d_tmp_a); fre(c->d_tmp_b); fre(c->d_fleet[0]); fre(c->d_fleet[1]);
   fre(c->d_cc); fre(c->d_QS); fre(c->d_QT); fre(c->d_QH); fre(c->d_QP); fre(c->d_pred); fre(c->d_wf); fre(c->d_govf); fre(c->d_mg_grp); fre(c->d_mg_wl); fre(c->d_mg_anch);
   if (c->h_cc) (void)hipHostFree(c->h_cc);
   if (c->h_flags) (void)hipHostFree(c->h_flags);
   if (c->h_hreq) (void)hipHostFree(c->h_hreq);
   if (c->h_hrep) (void)hipHostFree(c->h_hrep);
+  if (c->h_fleet) (void)hipHostFree(c->h_fleet);
   if (c->h_stat) hipHostFree(c->h_stat);
   if (c->h_ctl) hipHostFree(c->h_ctl);
   for (auto& e : c->pending) {
@@ -2419,6 +2430,16 @@ int tsw_step(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n) {
   return TSW_OK;
 }
 
+// k_decide's arrays on the device: what tsw_decide uploads and tsw_decide_fleet builds there
+struct DecideDev {
+  uint32_t n, tot;
+  uint32_t *v, *g, *off, *nv, *ng;  // inputs: n, n, n + 1, max(tot, 1), max(tot, 1) words
+  uint32_t *act, *cell, *par, *np;  // outputs: n words each
+  uint32_t* part;                   // tot + n words (DecideArgs::part)
+  uint32_t *q0, *q1, *cnt;          // the rounds' agent lists (n words each) and their 2 counters
+};
+static int decide_rounds(tsw_ctx* c, const DecideDev& D);
+
 static int decide_impl(tsw_ctx* c, const uint32_t* my_v, const uint32_t* my_g, uint32_t n, const uint32_t* nb_off,
                        const uint32_t* nb_v, const uint32_t* nb_g, uint32_t* act, uint32_t* cell, uint32_t* partner,
                        uint32_t* npart, uint32_t* part) {
@@ -2445,100 +2466,99 @@ static int decide_impl(tsw_ctx* c, const uint32_t* my_v, const uint32_t* my_g, u
   TRY(ensure_tables(c, goals, true));
   // device copies: inputs, outputs, pending lists (ping-pong)
   const size_t nb = std::max<uint32_t>(tot, 1u);
+  struct DevBuf {
+    uint32_t* p = nullptr;
+    ~DevBuf() {
+      if (p) (void)hipFree(p);
+    }
+  } buf;
+  const size_t words = 2 * (size_t)n + (n + 1) + 2 * nb + 4 * (size_t)n + (tot + n) + 2 * (size_t)n + 2;
+  HIPCHK(hipMalloc(&buf.p, words * 4));
+  DecideDev D{};
+  D.n = n;
+  D.tot = tot;
+  D.v = buf.p;
+  D.g = D.v + n;
+  D.off = D.g + n;
+  D.nv = D.off + n + 1;
+  D.ng = D.nv + nb;
+  D.act = D.ng + nb;
+  D.cell = D.act + n;
+  D.par = D.cell + n;
+  D.np = D.par + n;
+  D.part = D.np + n;
+  D.q0 = D.part + tot + n;
+  D.q1 = D.q0 + n;
+  D.cnt = D.q1 + n;
+  HIPCHK(hipMemcpyAsync(D.v, my_v, n * 4ull, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemcpyAsync(D.g, my_g, n * 4ull, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemcpyAsync(D.off, nb_off, (n + 1) * 4ull, hipMemcpyHostToDevice, c->s));
+  if (tot) {
+    HIPCHK(hipMemcpyAsync(D.nv, nb_v, tot * 4ull, hipMemcpyHostToDevice, c->s));
+    HIPCHK(hipMemcpyAsync(D.ng, nb_g, tot * 4ull, hipMemcpyHostToDevice, c->s));
+  }
+  TRY(decide_rounds(c, D));
+  HIPCHK(hipMemcpyAsync(act, D.act, n * 4ull, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipMemcpyAsync(cell, D.cell, n * 4ull, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipMemcpyAsync(partner, D.par, n * 4ull, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipMemcpyAsync(npart, D.np, n * 4ull, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipMemcpyAsync(part, D.part, ((size_t)tot + n) * 4ull, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipStreamSynchronize(c->s));
+  resolve_timing(c);
+  return TSW_OK;
+}
+
+// The decision rounds over device-resident lists, shared by tsw_decide and tsw_decide_fleet: k_decide
+// over every agent, K3 over the pairs it queued, k_decide again over the agents it parked, until none
+// is pending. The outputs stay on the device; the stream is idle when this returns TSW_OK.
+static int decide_rounds(tsw_ctx* c, const DecideDev& D) {
+  const uint32_t n = D.n, tot = D.tot;
   std::vector<uint32_t> idx(n);
   for (uint32_t i = 0; i < n; ++i) idx[i] = i;
-  uint32_t* d = nullptr;
-  const size_t words = 2 * (size_t)n + (n + 1) + 2 * nb + 4 * (size_t)n + (tot + n) + 2 * (size_t)n + 2;
-  HIPCHK(hipMalloc(&d, words * 4));
-  uint32_t *d_v = d, *d_g = d_v + n, *d_off = d_g + n, *d_nv = d_off + n + 1, *d_ng = d_nv + nb;
-  uint32_t *d_act = d_ng + nb, *d_cell = d_act + n, *d_par = d_cell + n, *d_np = d_par + n;
-  uint32_t *d_part = d_np + n, *d_q0 = d_part + tot + n, *d_q1 = d_q0 + n, *d_cnt = d_q1 + n;
-  auto cleanup = [&]() { hipFree(d); };
-  auto fail = [&](hipError_t e) {
-    cleanup();
-    c->err = std::string("HIP: ") + hipGetErrorString(e);
-    return TSW_EHIP;
-  };
-  hipError_t e;
-#define DCHK(x)                                 \
-  do {                                          \
-    if ((e = (x)) != hipSuccess) return fail(e); \
-  } while (0)
-  DCHK(hipMemcpyAsync(d_v, my_v, n * 4ull, hipMemcpyHostToDevice, c->s));
-  DCHK(hipMemcpyAsync(d_g, my_g, n * 4ull, hipMemcpyHostToDevice, c->s));
-  DCHK(hipMemcpyAsync(d_off, nb_off, (n + 1) * 4ull, hipMemcpyHostToDevice, c->s));
-  if (tot) {
-    DCHK(hipMemcpyAsync(d_nv, nb_v, tot * 4ull, hipMemcpyHostToDevice, c->s));
-    DCHK(hipMemcpyAsync(d_ng, nb_g, tot * 4ull, hipMemcpyHostToDevice, c->s));
-  }
-  DCHK(hipMemcpyAsync(d_q0, idx.data(), n * 4ull, hipMemcpyHostToDevice, c->s));
-  if (int r = ensure_queue(c, std::max<size_t>(2 * ((size_t)n + tot), 1024)); r != TSW_OK) {
-    cleanup();
-    return r;
-  }
+  HIPCHK(hipMemcpyAsync(D.q0, idx.data(), n * 4ull, hipMemcpyHostToDevice, c->s));
+  TRY(ensure_queue(c, std::max<size_t>(2 * ((size_t)n + tot), 1024)));
   DecideArgs A{};
   A.W = c->G.W;
   A.ncell = c->G.ncell;
-  A.my_v = d_v;
-  A.my_g = d_g;
-  A.nb_off = d_off;
-  A.nb_v = d_nv;
-  A.nb_g = d_ng;
+  A.my_v = D.v;
+  A.my_g = D.g;
+  A.nb_off = D.off;
+  A.nb_v = D.nv;
+  A.nb_g = D.ng;
   A.nbmask = c->d_nbmask;
   A.goal_tab = c->d_goal_tab;
   A.nh = c->d_nh;
   A.nstride = c->tstride;
-  A.act = d_act;
-  A.cell = d_cell;
-  A.partner = d_par;
-  A.npart = d_np;
-  A.part = d_part;
+  A.act = D.act;
+  A.cell = D.cell;
+  A.partner = D.par;
+  A.npart = D.np;
+  A.part = D.part;
   A.Q = c->d_Q;
   A.qcap = (uint32_t)c->qcap;
   A.err = &c->d_stat->err;
   uint32_t nq = n;
-  uint32_t* qin = d_q0;
-  uint32_t* qout = d_q1;
+  uint32_t* qin = D.q0;
+  uint32_t* qout = D.q1;
   for (int round = 0; nq > 0; ++round) {
-    if (round > 1 + 2 * (int)std::min<uint64_t>(tot + n, 1u << 20)) {
-      cleanup();
-      RET(TSW_EINVAL, "decision made no progress");
-    }
+    if (round > 1 + 2 * (int)std::min<uint64_t>((uint64_t)tot + n, 1u << 20)) RET(TSW_EINVAL, "decision made no progress");
     A.qidx = qin;
     A.nq = nq;
     A.pending_out = qout;
-    A.qcount = d_cnt;
-    A.npending = d_cnt + 1;
-    DCHK(hipMemsetAsync(d_cnt, 0, 8, c->s));
-    DCHK(launch_decide(A, c->s));
+    A.qcount = D.cnt;
+    A.npending = D.cnt + 1;
+    HIPCHK(hipMemsetAsync(D.cnt, 0, 8, c->s));
+    HIPCHK(launch_decide(A, c->s));
     uint32_t h[2] = {0, 0};
-    DCHK(hipMemcpyAsync(h, d_cnt, 8, hipMemcpyDeviceToHost, c->s));
-    DCHK(hipStreamSynchronize(c->s));
-    if (int r = check_err(c); r != TSW_OK) {
-      cleanup();
-      return r;
-    }
+    HIPCHK(hipMemcpyAsync(h, D.cnt, 8, hipMemcpyDeviceToHost, c->s));
+    HIPCHK(hipStreamSynchronize(c->s));
+    TRY(check_err(c));
     if (h[1] == 0) break;
-    if (h[0] == 0 || h[0] > c->qcap) {
-      cleanup();
-      RET(TSW_EINVAL, "decision stalled on an unresolvable next hop");
-    }
-    if (int r = run_astar(c, c->d_Q, h[0], true, nullptr, nullptr); r != TSW_OK) {
-      cleanup();
-      return r;
-    }
+    if (h[0] == 0 || h[0] > c->qcap) RET(TSW_EINVAL, "decision stalled on an unresolvable next hop");
+    TRY(run_astar(c, c->d_Q, h[0], true, nullptr, nullptr));
     nq = h[1];
     std::swap(qin, qout);
   }
-  DCHK(hipMemcpyAsync(act, d_act, n * 4ull, hipMemcpyDeviceToHost, c->s));
-  DCHK(hipMemcpyAsync(cell, d_cell, n * 4ull, hipMemcpyDeviceToHost, c->s));
-  DCHK(hipMemcpyAsync(partner, d_par, n * 4ull, hipMemcpyDeviceToHost, c->s));
-  DCHK(hipMemcpyAsync(npart, d_np, n * 4ull, hipMemcpyDeviceToHost, c->s));
-  DCHK(hipMemcpyAsync(part, d_part, ((size_t)tot + n) * 4ull, hipMemcpyDeviceToHost, c->s));
-  DCHK(hipStreamSynchronize(c->s));
-#undef DCHK
-  cleanup();
-  resolve_timing(c);
   return TSW_OK;
 }
 
@@ -2549,6 +2569,175 @@ int tsw_decide(tsw_ctx* c, const uint32_t* my_v, const uint32_t* my_g, uint32_t 
   NOT_FROM_RESOLVER(c);
   // a failed round may leave queued pairs PENDING: reset them before returning the error
   return reset_pending_after(c, decide_impl(c, my_v, my_g, n, nb_off, nb_v, nb_g, act, cell, partner, npart, part));
+}
+
+// ---- K5: fleet-wide nearby lists (tsw_nearby.hip) and the decentralized tick built on them ----------
+
+static int fleet_grow(tsw_ctx* c, int which, size_t words) {
+  if (words <= c->fleet_cap[which] && c->d_fleet[which]) return TSW_OK;
+  HIPCHK(hipStreamSynchronize(c->s));
+  HIPCHK(dgrow(c->d_fleet[which], c->fleet_cap[which], words));
+  return TSW_OK;
+}
+
+// pinned host staging (grow-only): one copy each way instead of one pageable copy per array
+static int fleet_hgrow(tsw_ctx* c, size_t words) {
+  if (words <= c->h_fleet_cap && c->h_fleet) return TSW_OK;
+  HIPCHK(hipStreamSynchronize(c->s));
+  if (c->h_fleet) HIPCHK(hipHostFree(c->h_fleet));
+  c->h_fleet = nullptr;
+  c->h_fleet_cap = 0;
+  HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_fleet), words * 4, hipHostMallocDefault));
+  c->h_fleet_cap = words;
+  return TSW_OK;
+}
+
+// The first half of both entry points: v (and g) on the device, the bins, every list's length and the
+// offsets (A.off = nb_off, on the device), with the lists' total and the longest list read back.
+struct FleetLists {
+  NearbyArgs A{};
+  uint32_t *v = nullptr, *g = nullptr;  // device copies (g only when given)
+  uint32_t total = 0, maxlen = 0;
+};
+static int nearby_offsets(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t n, uint32_t radius, FleetLists* S) {
+  const uint32_t ncell = c->G.ncell;
+  const size_t nbs = std::max(nb_scan_blocks(ncell), nb_scan_blocks(n));
+  TRY(fleet_grow(c, 0, 4 + 2 * (size_t)n + ((size_t)ncell + 1) + 2 * (size_t)n + ((size_t)n + 1) + nbs));
+  TRY(fleet_hgrow(c, 4 * (size_t)n + 4));
+  uint32_t* d = c->d_fleet[0];
+  NearbyArgs& A = S->A;
+  A.total64 = reinterpret_cast<unsigned long long*>(d);  // words 0-1 (the allocation is 8-byte aligned)
+  A.maxlen = d + 2;
+  A.cell_start = d + 4;  // right behind them: launch_nearby_count clears all three with one memset
+  S->v = A.cell_start + ncell + 1;
+  S->g = S->v + n;
+  A.rank = S->g + n;
+  A.sorted = A.rank + n;
+  A.off = A.sorted + n;
+  A.bsum = A.off + n + 1;
+  A.W = c->G.W;
+  A.H = c->G.H;
+  A.n = n;
+  A.radius = std::min(radius, c->G.W + c->G.H);  // farther than any two cells of the grid are apart
+  A.v = S->v;
+  // v | g through the staging buffer in one copy (S->g follows S->v on the device); the stream orders
+  // the read-back below behind it, so the same buffer takes the count pass's head words
+  std::memcpy(c->h_fleet, v, n * 4ull);
+  if (g) std::memcpy(c->h_fleet + n, g, n * 4ull);
+  HIPCHK(hipMemcpyAsync(S->v, c->h_fleet, (g ? 2ull : 1ull) * n * 4ull, hipMemcpyHostToDevice, c->s));
+  HIPCHK(launch_nearby_count(A, c->s));
+  HIPCHK(hipMemcpyAsync(c->h_fleet, d, 16, hipMemcpyDeviceToHost, c->s));  // total64, maxlen, pad
+  HIPCHK(hipStreamSynchronize(c->s));
+  unsigned long long tot64 = 0;
+  std::memcpy(&tot64, c->h_fleet, 8);
+  S->maxlen = c->h_fleet[2];
+  if (tot64 > 0xFFFFFFFFull) RET(TSW_EOVERFLOW, "the nearby lists hold more than 2^32 - 1 entries");
+  S->total = (uint32_t)tot64;
+  return TSW_OK;
+}
+
+int tsw_nearby(tsw_ctx* c, const uint32_t* v, uint32_t n, uint32_t radius, uint32_t* nb_off, uint32_t* nb_idx,
+               uint32_t cap, uint32_t* total) {
+  if (!c) return TSW_EINVAL;
+  NOT_FROM_RESOLVER(c);
+  if (!nb_off || !total) RET(TSW_EINVAL, "null argument");
+  nb_off[0] = 0;
+  *total = 0;
+  if (n == 0) return TSW_OK;
+  if (!v) RET(TSW_EINVAL, "null argument");
+  for (uint32_t i = 0; i < n; ++i)
+    if (v[i] >= c->G.ncell) RET(TSW_EINVAL, "agent cell off-grid");
+  TRY(set_device(c));
+  FleetLists S;
+  TRY(nearby_offsets(c, v, nullptr, n, radius, &S));
+  HIPCHK(hipMemcpyAsync(nb_off, S.A.off, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipStreamSynchronize(c->s));
+  *total = S.total;
+  if (S.total > cap) RET(TSW_EOVERFLOW, "nb_idx is too small for the nearby lists (*total entries)");
+  if (S.total == 0) return TSW_OK;
+  if (!nb_idx) RET(TSW_EINVAL, "null nb_idx");
+  TRY(fleet_grow(c, 1, S.total));
+  HIPCHK(launch_nearby_fill(S.A, S.maxlen, c->d_fleet[1], nullptr, nullptr, nullptr, c->s));
+  HIPCHK(hipMemcpyAsync(nb_idx, c->d_fleet[1], (size_t)S.total * 4, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipStreamSynchronize(c->s));
+  return TSW_OK;
+}
+
+static int decide_fleet_impl(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t n, uint32_t radius,
+                             uint32_t* act, uint32_t* cell, uint32_t* partner, uint32_t* part_off, uint32_t* part,
+                             uint32_t part_cap) {
+  std::vector<uint32_t> goals;
+  goals.reserve(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!cell_id_ok(c, v[i]) || !cell_id_ok(c, g[i]))
+      RET(TSW_EINVAL, "agent cell or goal off-grid or blocked (reference panics at agent.rs:358)");
+    goals.push_back(g[i]);
+  }
+  // every list entry is an agent of the fleet: the goals a decision can route to are the fleet's own
+  TRY(ensure_tables(c, goals, true));
+  FleetLists S;
+  TRY(nearby_offsets(c, v, g, n, radius, &S));
+  const uint32_t tot = S.total;
+  const size_t nb = std::max<uint32_t>(tot, 1u);
+  TRY(fleet_grow(c, 1, 3 * nb + 4 * (size_t)n + 2 * ((size_t)tot + n) + 2 * (size_t)n + 2 + ((size_t)n + 1)));
+  uint32_t* d_idx = c->d_fleet[1];
+  DecideDev D{};
+  D.n = n;
+  D.tot = tot;
+  D.v = S.v;
+  D.g = S.g;
+  D.off = S.A.off;
+  D.nv = d_idx + nb;
+  D.ng = D.nv + nb;
+  D.act = D.ng + nb;  // act | cell | partner | part_off: one block, one copy back
+  D.cell = D.act + n;
+  D.par = D.cell + n;
+  uint32_t* d_poff = D.par + n;        // n + 1: participant offsets
+  D.np = d_poff + n + 1;
+  D.part = D.np + n;
+  D.q0 = D.part + tot + n;
+  D.q1 = D.q0 + n;
+  D.cnt = D.q1 + n;
+  uint32_t* d_pout = D.cnt + 2;        // tot + n: compacted participants (agent indices)
+  // the lists, and in the same pass their cells and goals (nb_v / nb_g, what k_decide reads)
+  HIPCHK(launch_nearby_fill(S.A, S.maxlen, d_idx, S.g, D.nv, D.ng, c->s));
+  TRY(decide_rounds(c, D));
+  // list indices -> agent indices; participants compacted behind the scan of npart (the kernel itself
+  // compares part_off[n] with part_cap, so the common tick without a rotation ends in one synchronise)
+  HIPCHK(hipMemcpyAsync(d_poff, D.np, n * 4ull, hipMemcpyDeviceToDevice, c->s));
+  HIPCHK(launch_exclusive_scan(d_poff, n, S.A.bsum, c->s));
+  HIPCHK(launch_fleet_finish(n, D.off, d_idx, D.par, D.np, D.part, d_poff, d_pout, part_cap, c->s));
+  HIPCHK(hipMemcpyAsync(c->h_fleet, D.act, (4 * (size_t)n + 1) * 4, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipStreamSynchronize(c->s));
+  std::memcpy(act, c->h_fleet, n * 4ull);
+  std::memcpy(cell, c->h_fleet + n, n * 4ull);
+  std::memcpy(partner, c->h_fleet + 2 * (size_t)n, n * 4ull);
+  std::memcpy(part_off, c->h_fleet + 3 * (size_t)n, ((size_t)n + 1) * 4);
+  const uint32_t ptot = part_off[n];
+  if (ptot > part_cap) {
+    resolve_timing(c);
+    RET(TSW_EOVERFLOW, "part is too small for the rotation participants (part_off[n] entries)");
+  }
+  if (ptot) {
+    if (!part) RET(TSW_EINVAL, "null part");
+    HIPCHK(hipMemcpyAsync(part, d_pout, (size_t)ptot * 4, hipMemcpyDeviceToHost, c->s));
+    HIPCHK(hipStreamSynchronize(c->s));
+  }
+  resolve_timing(c);
+  return TSW_OK;
+}
+
+int tsw_decide_fleet(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t n, uint32_t radius, uint32_t* act,
+                     uint32_t* cell, uint32_t* partner, uint32_t* part_off, uint32_t* part, uint32_t part_cap) {
+  if (!c) return TSW_EINVAL;
+  NOT_FROM_RESOLVER(c);
+  if (!part_off) RET(TSW_EINVAL, "null argument");
+  part_off[0] = 0;
+  if (n == 0) return TSW_OK;
+  if (!v || !g || !act || !cell || !partner) RET(TSW_EINVAL, "null argument");
+  TRY(set_device(c));
+  // a failed round may leave queued pairs PENDING: reset them before returning the error
+  return reset_pending_after(c, decide_fleet_impl(c, v, g, n, radius, act, cell, partner, part_off, part, part_cap));
 }
 
 int tsw_get_path_next(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, uint32_t k, uint32_t* next,

@@ -35,7 +35,7 @@ pub const TSW_ENODEV: c_int = -19;
 
 /// ABI revision of include/tswap.h this crate mirrors; `Planner::new` refuses a library built
 /// against another one.
-pub const TSW_ABI_VERSION: c_int = 7;
+pub const TSW_ABI_VERSION: c_int = 8;
 
 /// `TswOpts::host_astar`: no host A* service.
 pub const TSW_HOST_ASTAR_OFF: u32 = 0xFFFFFFFF;
@@ -160,6 +160,11 @@ extern "C" {
     pub fn tsw_decide(ctx: *mut TswCtx, my_v: *const u32, my_g: *const u32, n: u32, nb_off: *const u32,
                       nb_v: *const u32, nb_g: *const u32, act: *mut u32, cell: *mut u32, partner: *mut u32,
                       npart: *mut u32, part: *mut u32) -> c_int;
+    pub fn tsw_nearby(ctx: *mut TswCtx, v: *const u32, n: u32, radius: u32, nb_off: *mut u32, nb_idx: *mut u32,
+                      cap: u32, total: *mut u32) -> c_int;
+    pub fn tsw_decide_fleet(ctx: *mut TswCtx, v: *const u32, g: *const u32, n: u32, radius: u32, act: *mut u32,
+                            cell: *mut u32, partner: *mut u32, part_off: *mut u32, part: *mut u32,
+                            part_cap: u32) -> c_int;
     pub fn tsw_dist_tables(ctx: *mut TswCtx, goals: *const u32, k: u32, out: *mut u16) -> c_int;
     pub fn tsw_dist_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_out: *mut u16) -> c_int;
     pub fn tsw_import_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_tables: *const u16) -> c_int;
@@ -451,6 +456,59 @@ impl Planner {
                 (act[i], cell[i], partner[i], part[b..b + npart[i] as usize].to_vec())
             })
             .collect())
+    }
+
+    /// `NearbyAgents::get_nearby` (agent.rs:108-153) for the whole fleet on the device: (nb_off, nb_idx)
+    /// with agent i's list the agent indices nb_idx[nb_off[i]..nb_off[i+1]] — every j != i within
+    /// Manhattan `radius` of cell v[i], in ascending index.
+    pub fn nearby(&mut self, v: &[u32], radius: u32) -> Result<(Vec<u32>, Vec<u32>), TswapError> {
+        let n = v.len();
+        let mut off = vec![0u32; n + 1];
+        let mut total = 0u32;
+        // size query first: TSW_EOVERFLOW with `total` valid whenever the lists are not empty
+        let rc = unsafe {
+            tsw_nearby(self.ctx, v.as_ptr(), n as u32, radius, off.as_mut_ptr(), std::ptr::null_mut(), 0, &mut total)
+        };
+        if rc != TSW_EOVERFLOW || total == 0 {
+            self.check(rc)?;
+            return Ok((off, Vec::new()));
+        }
+        let mut idx = vec![0u32; total as usize];
+        self.check(unsafe {
+            tsw_nearby(self.ctx, v.as_ptr(), n as u32, radius, off.as_mut_ptr(), idx.as_mut_ptr(), total, &mut total)
+        })?;
+        Ok((off, idx))
+    }
+
+    /// One decentralized tick for the fleet (tsw_decide_fleet): nearby lists and
+    /// `compute_next_move_with_tswap` for every agent, on the device. Returns (act, cell, partner,
+    /// part_off, part): partner[i] is an AGENT index (u32::MAX: none) and agent i's rotation
+    /// participants are the agent indices part[part_off[i]..part_off[i+1]].
+    #[allow(clippy::type_complexity)]
+    pub fn decide_fleet(&mut self, v: &[u32], g: &[u32], radius: u32)
+                        -> Result<(Vec<u32>, Vec<u32>, Vec<u32>, Vec<u32>, Vec<u32>), TswapError> {
+        let n = v.len();
+        if g.len() != n {
+            return Err(TswapError { code: TSW_EINVAL, message: "v and g lengths differ".into() });
+        }
+        let (mut act, mut cell, mut partner) = (vec![0u32; n], vec![0u32; n], vec![0u32; n]);
+        let mut off = vec![0u32; n + 1];
+        let mut part = vec![0u32; 4 * n + 64];
+        let mut rc = unsafe {
+            tsw_decide_fleet(self.ctx, v.as_ptr(), g.as_ptr(), n as u32, radius, act.as_mut_ptr(), cell.as_mut_ptr(),
+                             partner.as_mut_ptr(), off.as_mut_ptr(), part.as_mut_ptr(), part.len() as u32)
+        };
+        if rc == TSW_EOVERFLOW && off[n] as usize > part.len() {
+            part = vec![0u32; off[n] as usize];  // part was too small: part_off[n] is what it takes
+            rc = unsafe {
+                tsw_decide_fleet(self.ctx, v.as_ptr(), g.as_ptr(), n as u32, radius, act.as_mut_ptr(),
+                                 cell.as_mut_ptr(), partner.as_mut_ptr(), off.as_mut_ptr(), part.as_mut_ptr(),
+                                 part.len() as u32)
+            };
+        }
+        self.check(rc)?;
+        part.truncate(off[n] as usize);
+        Ok((act, cell, partner, off, part))
     }
 
     /// K1 distance tables (u16 per cell, TSW_DIST_INF blocked / unreachable), goal-major.
