@@ -65,7 +65,9 @@ extern "C" {
  * tsw_plan_mapd_resolved / tsw_next_hop_codes; 5: tsw_build_id, entry points refuse re-entry from a
  * tsw_plan_mapd_resolved resolver (TSW_EINVAL); 6: tsw_stats coop_worker_queries / coop_worker_pops;
  * 7: tsw_opts.reserved became host_astar, tsw_stats gained host_astar_queries / host_astar_used /
- * host_astar_ms, tsw_host_next_hop_codes; 8: tsw_nearby, tsw_decide_fleet. */
+ * host_astar_ms, tsw_host_next_hop_codes; 8: tsw_nearby, tsw_decide_fleet. Still 8: tsw_fleet_apply and
+ * tsw_fleet_run were added without touching a struct or an existing signature; a caller that wants
+ * them looks the two symbols up (dlsym) instead of comparing the revision. */
 #define TSW_ABI_VERSION 8
 
 /* AgentState discriminants in declaration order (src/map/agent.rs:9-15) */
@@ -245,6 +247,58 @@ int tsw_nearby(tsw_ctx *ctx, const uint32_t *v, uint32_t n, uint32_t radius,
 int tsw_decide_fleet(tsw_ctx *ctx, const uint32_t *v, const uint32_t *g, uint32_t n, uint32_t radius,
                      uint32_t *act, uint32_t *cell, uint32_t *partner,
                      uint32_t *part_off, uint32_t *part, uint32_t part_cap);
+
+/* The decentralized mode in lock step. The reference's agents gossip asynchronously; the transport is
+ * not modelled. What is modelled is the effect of the timer branch (bin/decentralized/agent.rs:838-927)
+ * and of the message handlers it triggers, under one deterministic schedule:
+ *   - in one TICK every agent runs the timer branch once, on fresh information: everyone's broadcast
+ *     position and goal are the tick-start arrays v0, g0;
+ *   - each agent's outgoing messages are delivered and handled before the next agent's turn;
+ *   - agents take their turns in ASCENDING AGENT INDEX (the choice already made for the list order).
+ * With (act, cell, partner, part_off, part) = tsw_decide_fleet(v0, g0, radius) and G a copy of g0, for
+ * i = 0 .. n-1 in order:
+ *   TSW_ACT_MOVE (:854-857)       v1[i] = cell[i]. No collision check, as in the reference: two agents
+ *                                 may enter one cell (duplicate positions are legal inputs). Moves read
+ *                                 v0 only, so their order plays no part.
+ *   TSW_ACT_GOAL_SWAP, j = partner[i]
+ *                                 (request :892-905, the partner's handler :1041-1072, the response
+ *                                 :1075-1087) the partner takes the requester's goal and answers with
+ *                                 the goal it held: G[i] and G[j] are exchanged, at their values of turn i.
+ *   TSW_ACT_ROTATION, P = part[part_off[i] .. part_off[i+1]), k = |P|
+ *                                 (request :907-920, handler :1090-1107) for m = 0 .. k-1:
+ *                                 G[P[m]] = g0[P[(m+1) % k]]. The request carries the goals of the
+ *                                 initiator's nearby information, i.e. the tick-start g0, not G. As in
+ *                                 the reference the initiator is not among its own participants and
+ *                                 keeps its goal.
+ *   TSW_ACT_WAIT                  nothing.
+ * Every other v1[i] = v0[i]; g1 = G. Left out — the caller's business between calls: the agent's
+ * bookkeeping (pending_goal_swap is always cleared within the tick; pending_rotation is never cleared
+ * in the reference), task_state, my_task and the pickup / delivery hand-over.
+ *
+ * tsw_fleet_apply: one tick's decisions, in tsw_decide_fleet's output form (they may be the caller's
+ * own), applied to v and g in place with exactly the sequential semantics above. TSW_EINVAL with v and g
+ * untouched, checked on the host before anything is launched: an act > 3; a Move cell off-grid or
+ * blocked; a swap partner >= n; a participant >= n; a rotation with fewer than 2 participants or one
+ * that lists a participant twice; a part_off that is not non-decreasing. n == 0: TSW_OK. */
+int tsw_fleet_apply(tsw_ctx *ctx, uint32_t *v, uint32_t *g, uint32_t n,
+                    const uint32_t *act, const uint32_t *cell, const uint32_t *partner,
+                    const uint32_t *part_off, const uint32_t *part);
+
+/* Up to `ticks` ticks of the model with v and g resident on the device: per tick the lists, the decisions
+ * (the tsw_decide_fleet pipeline) and their application; lists and decisions never visit the host.
+ * v, g are checked as tsw_decide_fleet checks them (TSW_EINVAL for a cell or goal off-grid or blocked).
+ * A tick is a pure function of (v, g), so a tick that changes neither is a fixed point: the run stops
+ * there and that tick is not counted. *ticks_done = the number of ticks that changed something; on
+ * return v and g hold the state after those ticks. v_rec / g_rec (each may be NULL): n * (ticks + 1)
+ * words, agent-major like tsw_plan_mapd's out — v_rec[i*(ticks+1) + t] = agent i's cell after t ticks;
+ * columns 0 .. *ticks_done are written, later columns are left untouched. ticks == 0: TSW_OK, column 0,
+ * *ticks_done = 0. n == 0: TSW_OK, *ticks_done = 0. A tick that fails (TSW_EOVERFLOW: a list of more
+ * than 1024 entries reaching Rule 4, or lists past 2^32 - 1 entries; TSW_ENOMEM; TSW_EHIP) returns its
+ * code with v, g and *ticks_done describing the state before that tick; the context stays usable.
+ * A run's goals stay inside the initial goal set (swaps permute goals, rotations copy g0 values) and its
+ * positions on free cells (moves are next hops): the inputs are validated once for all ticks. */
+int tsw_fleet_run(tsw_ctx *ctx, uint32_t *v, uint32_t *g, uint32_t n, uint32_t radius, uint32_t ticks,
+                  uint32_t *v_rec, uint32_t *g_rec, uint32_t *ticks_done);
 
 /* K1: BFS distance tables for k goal cells, u16 per cell, row-major
  * (TSW_DIST_INF for blocked/unreachable). out: host buffer k*w*h. */

@@ -124,7 +124,7 @@ EXPORTED_SYMBOLS = (
     "tsw_import_tables_device", "tsw_next_hop_tables", "tsw_next_hop_tables_device", "tsw_import_next_hops_device",
     "tsw_clear_tables", "tsw_get_stats", "tsw_reset_stats", "tsw_set_timing", "tsw_probe_round_floors",
     "tsw_abi_version", "tsw_plan_mapd_resolved", "tsw_next_hop_codes", "tsw_build_id",
-    "tsw_host_next_hop_codes", "tsw_nearby", "tsw_decide_fleet",
+    "tsw_host_next_hop_codes", "tsw_nearby", "tsw_decide_fleet", "tsw_fleet_apply", "tsw_fleet_run",
 )
 
 # tsw_resolve_fn (include/tswap.h): int (*)(void *user, uint32_t k, const uint32_t *start,
@@ -171,6 +171,10 @@ def load_library(path: str = LIB_PATH):
     lib.tsw_nearby.restype = ctypes.c_int
     lib.tsw_decide_fleet.argtypes = [vp, P(u32), P(u32), u32, u32, P(u32), P(u32), P(u32), P(u32), P(u32), u32]
     lib.tsw_decide_fleet.restype = ctypes.c_int
+    lib.tsw_fleet_apply.argtypes = [vp, P(u32), P(u32), u32, P(u32), P(u32), P(u32), P(u32), P(u32)]
+    lib.tsw_fleet_apply.restype = ctypes.c_int
+    lib.tsw_fleet_run.argtypes = [vp, P(u32), P(u32), u32, u32, u32, P(u32), P(u32), P(u32)]
+    lib.tsw_fleet_run.restype = ctypes.c_int
     lib.tsw_dist_tables.argtypes = [vp, P(u32), u32, P(ctypes.c_uint16)]
     lib.tsw_dist_tables_device.argtypes = [vp, P(u32), u32, vp]
     lib.tsw_import_tables_device.argtypes = [vp, P(u32), u32, vp]
@@ -455,6 +459,46 @@ class Planner:
             cap = int(off[n])
         self._check(rc)
         return act, cell, partner, off, part[:int(off[n])]
+
+    def fleet_apply(self, v, g, act, cell, partner, part_off, part):
+        """One tick's decisions (decide_fleet's outputs, or the caller's own in that form) applied in the
+        lock-step model of include/tswap.h: Moves, goal swaps and rotations with the reference handlers'
+        sequential semantics, agents taking their turns in ascending index. Works on copies, like step.
+        Returns (v, g) after the tick."""
+        v = np.ascontiguousarray(v, dtype=np.uint32).copy()
+        g = np.ascontiguousarray(g, dtype=np.uint32).copy()
+        act, cell, partner, part_off, part = (np.ascontiguousarray(a, dtype=np.uint32)
+                                              for a in (act, cell, partner, part_off, part))
+        n = v.size
+        if g.size != n or act.size != n or cell.size != n or partner.size != n or part_off.size != n + 1:
+            raise TswapError(TSW_EINVAL, "v, g, act, cell, partner need n entries and part_off n + 1")
+        if n and part.size < int(part_off.max()):
+            raise TswapError(TSW_EINVAL, "part is shorter than part_off says")
+        self._check(self._lib.tsw_fleet_apply(self._ctx, _u32p(v), _u32p(g), n, _u32p(act), _u32p(cell),
+                                              _u32p(partner), _u32p(part_off), _u32p(part) if part.size else None))
+        return v, g
+
+    def fleet_run(self, v, g, ticks: int, radius: int = 15, record: bool = False):
+        """Up to `ticks` lock-step ticks (lists, decisions, application) with v and g resident on the
+        device (tsw_fleet_run); stops early at a fixed point. Returns (v, g, ticks_done), with
+        record=True also (v_rec, g_rec) of shape (n, ticks_done + 1): column t is the state after t ticks."""
+        v = np.ascontiguousarray(v, dtype=np.uint32).copy()
+        g = np.ascontiguousarray(g, dtype=np.uint32).copy()
+        n = v.size
+        if g.size != n:
+            raise TswapError(TSW_EINVAL, "v and g must have the same length")
+        ticks = int(ticks)
+        done = ctypes.c_uint32(0)
+        vr = gr = None
+        if record:
+            vr = np.zeros((n, ticks + 1), dtype=np.uint32)
+            gr = np.zeros((n, ticks + 1), dtype=np.uint32)
+        self._check(self._lib.tsw_fleet_run(self._ctx, _u32p(v), _u32p(g), n, radius, ticks,
+                                            _u32p(vr) if record else None, _u32p(gr) if record else None,
+                                            ctypes.byref(done)))
+        if record:
+            return v, g, done.value, vr[:, :done.value + 1].copy(), gr[:, :done.value + 1].copy()
+        return v, g, done.value
 
     # --- get_path -----------------------------------------------------------
     def get_path_next(self, start: np.ndarray, goal: np.ndarray):

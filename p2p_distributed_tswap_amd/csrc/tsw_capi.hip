@@ -26,6 +26,7 @@
 #include "tsw_host_astar.h"
 #include "tsw_internal.h"
 #include "tsw_launch.h"
+#include "tsw_fleet.h"
 #include "tsw_nearby.h"
 #include "tsw_plan.h"
 #include "tswap.h"
@@ -346,8 +347,9 @@ struct tsw_ctx {
   size_t tmp_cap = 0;
   // tsw_nearby / tsw_decide_fleet scratch (grow-only): [0] bins, counts and offsets (sized by the fleet
   // and the grid), [1] the lists and k_decide's arrays (sized by the lists' total)
-  uint32_t* d_fleet[2] = {nullptr, nullptr};
-  size_t fleet_cap[2] = {0, 0};
+  // [2] tsw_fleet_run's records (v_rec | g_rec)
+  uint32_t* d_fleet[3] = {nullptr, nullptr, nullptr};
+  size_t fleet_cap[3] = {0, 0, 0};
   uint32_t* h_fleet = nullptr;  // pinned staging of tsw_decide_fleet: v | g up, act | cell | partner | part_off down
   size_t h_fleet_cap = 0;
 
@@ -2294,7 +2296,7 @@ void tsw_destroy(tsw_ctx* c) {
   fre(c->d_gt); fre(c->d_dec); fre(c->d_mu); fre(c->d_dups); fre(c->d_onc); fre(c->d_candc); fre(c->d_f1); fre(c->d_f2);
   if (c->h_dups) (void)hipHostFree(c->h_dups);
   fre(c->d_task); fre(c->d_occ); fre(c->d_nhc); fre(c->d_ctl); fre(c->d_pargs); fre(c->d_ticks); fre(c->d_dtag); fre(c->d_live); fre(c->d_klt); fre(c->d_kpos); fre(c->d_kbox); fre(c->d_kcnt); fre(c->d_pick); fre(c->d_dlv); fre(c->d_unused);
-  fre(c->d_rec); fre(c->d_grec); fre(c->d_tmp_a); fre(c->d_tmp_b); fre(c->d_fleet[0]); fre(c->d_fleet[1]);
+  fre(c->d_rec); fre(c->d_grec); fre(c->d_tmp_a); fre(c->d_tmp_b); fre(c->d_fleet[0]); fre(c->d_fleet[1]); fre(c->d_fleet[2]);
   fre(c->d_cc); fre(c->d_QS); fre(c->d_QT); fre(c->d_QH); fre(c->d_QP); fre(c->d_pred); fre(c->d_wf); fre(c->d_govf); fre(c->d_mg_grp); fre(c->d_mg_wl); fre(c->d_mg_anch);
   if (c->h_cc) (void)hipHostFree(c->h_cc);
   if (c->h_flags) (void)hipHostFree(c->h_flags);
@@ -2599,10 +2601,13 @@ struct FleetLists {
   uint32_t *v = nullptr, *g = nullptr;  // device copies (g only when given)
   uint32_t total = 0, maxlen = 0;
 };
-static int nearby_offsets(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t n, uint32_t radius, FleetLists* S) {
+// The buffers of the count pass in d_fleet[0] (sized by the fleet and the grid), with `extra` more words
+// behind them (*extra_out: tsw_fleet_run keeps its apply state there, next to the resident v | g).
+static int fleet_lists_setup(tsw_ctx* c, uint32_t n, uint32_t radius, FleetLists* S, size_t extra = 0,
+                             uint32_t** extra_out = nullptr) {
   const uint32_t ncell = c->G.ncell;
   const size_t nbs = std::max(nb_scan_blocks(ncell), nb_scan_blocks(n));
-  TRY(fleet_grow(c, 0, 4 + 2 * (size_t)n + ((size_t)ncell + 1) + 2 * (size_t)n + ((size_t)n + 1) + nbs));
+  TRY(fleet_grow(c, 0, 4 + 2 * (size_t)n + ((size_t)ncell + 1) + 2 * (size_t)n + ((size_t)n + 1) + nbs + extra));
   TRY(fleet_hgrow(c, 4 * (size_t)n + 4));
   uint32_t* d = c->d_fleet[0];
   NearbyArgs& A = S->A;
@@ -2615,25 +2620,41 @@ static int nearby_offsets(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint
   A.sorted = A.rank + n;
   A.off = A.sorted + n;
   A.bsum = A.off + n + 1;
+  if (extra_out) *extra_out = A.bsum + nbs;
   A.W = c->G.W;
   A.H = c->G.H;
   A.n = n;
   A.radius = std::min(radius, c->G.W + c->G.H);  // farther than any two cells of the grid are apart
   A.v = S->v;
-  // v | g through the staging buffer in one copy (S->g follows S->v on the device); the stream orders
-  // the read-back below behind it, so the same buffer takes the count pass's head words
-  std::memcpy(c->h_fleet, v, n * 4ull);
-  if (g) std::memcpy(c->h_fleet + n, g, n * 4ull);
-  HIPCHK(hipMemcpyAsync(S->v, c->h_fleet, (g ? 2ull : 1ull) * n * 4ull, hipMemcpyHostToDevice, c->s));
-  HIPCHK(launch_nearby_count(A, c->s));
+  return TSW_OK;
+}
+
+// The count pass over the device-resident S->v, with the lists' total and the longest list read back.
+// pad_src (device, may be nullptr) -> *pad: one more word for the host in the pad slot of the same 16-byte
+// read-back (tsw_fleet_run: the previous tick's "changed" word, so a tick adds no synchronise for it).
+static int fleet_lists_count(tsw_ctx* c, FleetLists* S, const uint32_t* pad_src = nullptr, uint32_t* pad = nullptr) {
+  uint32_t* d = c->d_fleet[0];
+  HIPCHK(launch_nearby_count(S->A, c->s));
+  if (pad_src) HIPCHK(hipMemcpyAsync(d + 3, pad_src, 4, hipMemcpyDeviceToDevice, c->s));
   HIPCHK(hipMemcpyAsync(c->h_fleet, d, 16, hipMemcpyDeviceToHost, c->s));  // total64, maxlen, pad
   HIPCHK(hipStreamSynchronize(c->s));
   unsigned long long tot64 = 0;
   std::memcpy(&tot64, c->h_fleet, 8);
   S->maxlen = c->h_fleet[2];
+  if (pad) *pad = c->h_fleet[3];
   if (tot64 > 0xFFFFFFFFull) RET(TSW_EOVERFLOW, "the nearby lists hold more than 2^32 - 1 entries");
   S->total = (uint32_t)tot64;
   return TSW_OK;
+}
+
+static int nearby_offsets(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t n, uint32_t radius, FleetLists* S) {
+  TRY(fleet_lists_setup(c, n, radius, S));
+  // v | g through the staging buffer in one copy (S->g follows S->v on the device); the stream orders
+  // the read-back of the count pass behind it, so the same buffer takes the count pass's head words
+  std::memcpy(c->h_fleet, v, n * 4ull);
+  if (g) std::memcpy(c->h_fleet + n, g, n * 4ull);
+  HIPCHK(hipMemcpyAsync(S->v, c->h_fleet, (g ? 2ull : 1ull) * n * 4ull, hipMemcpyHostToDevice, c->s));
+  return fleet_lists_count(c, S);
 }
 
 int tsw_nearby(tsw_ctx* c, const uint32_t* v, uint32_t n, uint32_t radius, uint32_t* nb_off, uint32_t* nb_idx,
@@ -2663,25 +2684,19 @@ int tsw_nearby(tsw_ctx* c, const uint32_t* v, uint32_t n, uint32_t radius, uint3
   return TSW_OK;
 }
 
-static int decide_fleet_impl(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t n, uint32_t radius,
-                             uint32_t* act, uint32_t* cell, uint32_t* partner, uint32_t* part_off, uint32_t* part,
-                             uint32_t part_cap) {
-  std::vector<uint32_t> goals;
-  goals.reserve(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    if (!cell_id_ok(c, v[i]) || !cell_id_ok(c, g[i]))
-      RET(TSW_EINVAL, "agent cell or goal off-grid or blocked (reference panics at agent.rs:358)");
-    goals.push_back(g[i]);
-  }
-  // every list entry is an agent of the fleet: the goals a decision can route to are the fleet's own
-  TRY(ensure_tables(c, goals, true));
-  FleetLists S;
-  TRY(nearby_offsets(c, v, g, n, radius, &S));
+// The device-resident middle of a tick, shared by tsw_decide_fleet and tsw_fleet_run: behind the count
+// pass (S), the lists with their cells and goals, the decision rounds, and the translation of list
+// indices to agent indices. The decisions stay on the device: D->act | D->cell | D->par | *d_poff (n + 1
+// participant offsets) in one block, the participants in *d_pout (S.total + n words; written when
+// part_off[n] <= part_cap).
+static int fleet_decide_device(tsw_ctx* c, const FleetLists& S, uint32_t part_cap, DecideDev* Dp, uint32_t** d_poff_out,
+                               uint32_t** d_pout_out) {
+  const uint32_t n = S.A.n;
   const uint32_t tot = S.total;
   const size_t nb = std::max<uint32_t>(tot, 1u);
   TRY(fleet_grow(c, 1, 3 * nb + 4 * (size_t)n + 2 * ((size_t)tot + n) + 2 * (size_t)n + 2 + ((size_t)n + 1)));
   uint32_t* d_idx = c->d_fleet[1];
-  DecideDev D{};
+  DecideDev& D = *Dp;
   D.n = n;
   D.tot = tot;
   D.v = S.v;
@@ -2707,6 +2722,28 @@ static int decide_fleet_impl(tsw_ctx* c, const uint32_t* v, const uint32_t* g, u
   HIPCHK(hipMemcpyAsync(d_poff, D.np, n * 4ull, hipMemcpyDeviceToDevice, c->s));
   HIPCHK(launch_exclusive_scan(d_poff, n, S.A.bsum, c->s));
   HIPCHK(launch_fleet_finish(n, D.off, d_idx, D.par, D.np, D.part, d_poff, d_pout, part_cap, c->s));
+  *d_poff_out = d_poff;
+  *d_pout_out = d_pout;
+  return TSW_OK;
+}
+
+static int decide_fleet_impl(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t n, uint32_t radius,
+                             uint32_t* act, uint32_t* cell, uint32_t* partner, uint32_t* part_off, uint32_t* part,
+                             uint32_t part_cap) {
+  std::vector<uint32_t> goals;
+  goals.reserve(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!cell_id_ok(c, v[i]) || !cell_id_ok(c, g[i]))
+      RET(TSW_EINVAL, "agent cell or goal off-grid or blocked (reference panics at agent.rs:358)");
+    goals.push_back(g[i]);
+  }
+  // every list entry is an agent of the fleet: the goals a decision can route to are the fleet's own
+  TRY(ensure_tables(c, goals, true));
+  FleetLists S;
+  TRY(nearby_offsets(c, v, g, n, radius, &S));
+  DecideDev D{};
+  uint32_t *d_poff, *d_pout;
+  TRY(fleet_decide_device(c, S, part_cap, &D, &d_poff, &d_pout));
   HIPCHK(hipMemcpyAsync(c->h_fleet, D.act, (4 * (size_t)n + 1) * 4, hipMemcpyDeviceToHost, c->s));
   HIPCHK(hipStreamSynchronize(c->s));
   std::memcpy(act, c->h_fleet, n * 4ull);
@@ -2738,6 +2775,224 @@ int tsw_decide_fleet(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t 
   TRY(set_device(c));
   // a failed round may leave queued pairs PENDING: reset them before returning the error
   return reset_pending_after(c, decide_fleet_impl(c, v, g, n, radius, act, cell, partner, part_off, part, part_cap));
+}
+
+// ---- K5b: a tick's decisions applied (tsw_fleet.hip), and the lock-step run built on both ------------
+
+// words of the apply state behind n agents: g0, owner, opflag (n + 1), ops (2 n), the scan's block sums,
+// the changed word
+static size_t fleet_apply_words(uint32_t n) { return 5 * (size_t)n + 1 + nb_scan_blocks(n) + 1; }
+static void fleet_apply_layout(FleetApplyArgs* A, uint32_t* p, uint32_t n) {
+  A->n = n;
+  A->g0 = p;
+  A->owner = A->g0 + n;
+  A->opflag = A->owner + n;
+  A->ops = A->opflag + n + 1;
+  A->bsum = A->ops + 2 * (size_t)n;
+  A->changed = A->bsum + nb_scan_blocks(n);
+}
+
+int tsw_fleet_apply(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n, const uint32_t* act, const uint32_t* cell,
+                    const uint32_t* partner, const uint32_t* part_off, const uint32_t* part) {
+  if (!c) return TSW_EINVAL;
+  NOT_FROM_RESOLVER(c);
+  if (n == 0) return TSW_OK;
+  if (!v || !g || !act || !cell || !partner || !part_off) RET(TSW_EINVAL, "null argument");
+  // everything a kernel would index with, checked before anything is launched
+  for (uint32_t i = 0; i < n; ++i)
+    if (part_off[i + 1] < part_off[i]) RET(TSW_EINVAL, "part_off must be non-decreasing");
+  const uint32_t pbase = part_off[0], ptot = part_off[n] - pbase;
+  std::vector<uint32_t> seen(n, 0u);  // seen[a] == i + 1: a is already a participant of rotation i
+  for (uint32_t i = 0; i < n; ++i) {
+    switch (act[i]) {
+      case TSW_ACT_MOVE:
+        if (!cell_id_ok(c, cell[i])) RET(TSW_EINVAL, "Move destination off-grid or blocked");
+        break;
+      case TSW_ACT_GOAL_SWAP:
+        if (partner[i] >= n) RET(TSW_EINVAL, "goal-swap partner is not an agent of the fleet");
+        break;
+      case TSW_ACT_ROTATION: {
+        if (part_off[i + 1] - part_off[i] < 2) RET(TSW_EINVAL, "rotation with fewer than 2 participants");
+        if (!part) RET(TSW_EINVAL, "null part");
+        for (uint32_t m = part_off[i]; m < part_off[i + 1]; ++m) {
+          const uint32_t a = part[m];
+          if (a >= n) RET(TSW_EINVAL, "rotation participant is not an agent of the fleet");
+          if (seen[a] == i + 1) RET(TSW_EINVAL, "rotation lists a participant twice");
+          seen[a] = i + 1;
+        }
+        break;
+      }
+      case TSW_ACT_WAIT: break;
+      default: RET(TSW_EINVAL, "act is not one of the four actions (0 .. 3)");
+    }
+  }
+  TRY(set_device(c));
+  // one block up: v | g | act | cell | partner | part_off (n + 1, rebased to 0) | part
+  const size_t in_words = 6 * (size_t)n + 1 + ptot;
+  TRY(fleet_grow(c, 1, in_words + fleet_apply_words(n)));
+  TRY(fleet_hgrow(c, in_words));
+  uint32_t* h = c->h_fleet;
+  std::memcpy(h, v, n * 4ull);
+  std::memcpy(h + n, g, n * 4ull);
+  std::memcpy(h + 2 * (size_t)n, act, n * 4ull);
+  std::memcpy(h + 3 * (size_t)n, cell, n * 4ull);
+  std::memcpy(h + 4 * (size_t)n, partner, n * 4ull);
+  for (uint32_t i = 0; i <= n; ++i) h[5 * (size_t)n + i] = part_off[i] - pbase;
+  if (ptot) std::memcpy(h + 6 * (size_t)n + 1, part + pbase, (size_t)ptot * 4);
+  uint32_t* d = c->d_fleet[1];
+  FleetApplyArgs A{};
+  A.v = d;
+  A.g = d + n;
+  A.act = d + 2 * (size_t)n;
+  A.cell = d + 3 * (size_t)n;
+  A.partner = d + 4 * (size_t)n;
+  A.part_off = d + 5 * (size_t)n;
+  A.part = d + 6 * (size_t)n + 1;
+  fleet_apply_layout(&A, d + in_words, n);
+  A.stamp = 1;
+  HIPCHK(hipMemcpyAsync(d, h, in_words * 4, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemsetAsync(A.changed, 0, 4, c->s));
+  HIPCHK(launch_fleet_apply(A, c->s));
+  // v | g, and the changed word behind them in the staging buffer
+  HIPCHK(hipMemcpyAsync(h, d, 2ull * n * 4, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipMemcpyAsync(h + 2 * (size_t)n, A.changed, 4, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipStreamSynchronize(c->s));
+  if (h[2 * (size_t)n] == FLEET_STUCK) RET(TSW_EHIP, "internal: the goal-op rounds made no progress");
+  std::memcpy(v, h, n * 4ull);
+  std::memcpy(g, h + n, n * 4ull);
+  return TSW_OK;
+}
+
+// v, g, *ticks_done and the records are written from the device state after `done` ticks; rc: the run's
+// result so far (a failing tick's code is kept, whatever the copy back does).
+static int fleet_run_finish(tsw_ctx* c, int rc, const FleetLists& S, FleetApplyArgs A, uint32_t moves_run, uint32_t done,
+                            uint32_t ticks, uint32_t* v, uint32_t* g, uint32_t* v_rec, uint32_t* g_rec,
+                            uint32_t* ticks_done) {
+  const uint32_t n = S.A.n;
+  const size_t stride = (size_t)ticks + 1;
+  auto copy_back = [&]() -> int {
+    if (moves_run == done) {  // column `done` is the state after the last tick: no moves kernel wrote it
+      A.rec_col = done;
+      HIPCHK(launch_fleet_record(A, c->s));
+    }
+    HIPCHK(hipMemcpyAsync(c->h_fleet, S.v, 2ull * n * 4, hipMemcpyDeviceToHost, c->s));
+    uint32_t* host_rec[2] = {v_rec, g_rec};
+    uint32_t* dev_rec[2] = {A.v_rec, A.g_rec};
+    for (int k = 0; k < 2; ++k) {
+      if (!host_rec[k]) continue;
+      if (done == ticks)
+        HIPCHK(hipMemcpyAsync(host_rec[k], dev_rec[k], n * stride * 4, hipMemcpyDeviceToHost, c->s));
+      else  // columns 0 .. done of every agent's row; the later ones stay as the caller left them
+        HIPCHK(hipMemcpy2DAsync(host_rec[k], stride * 4, dev_rec[k], stride * 4, ((size_t)done + 1) * 4, n,
+                                hipMemcpyDeviceToHost, c->s));
+    }
+    HIPCHK(hipStreamSynchronize(c->s));
+    std::memcpy(v, c->h_fleet, n * 4ull);
+    std::memcpy(g, c->h_fleet + n, n * 4ull);
+    *ticks_done = done;
+    return TSW_OK;
+  };
+  if (rc == TSW_OK) return copy_back();
+  if (rc != TSW_EHIP && done > 0) {  // done == 0: the caller's v and g are that state already
+    const std::string msg = c->err;
+    (void)copy_back();
+    c->err = msg;
+  }
+  return rc;
+}
+
+static int fleet_run_impl(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n, uint32_t radius, uint32_t ticks,
+                          uint32_t* v_rec, uint32_t* g_rec, uint32_t* ticks_done) {
+  std::vector<uint32_t> goals;
+  goals.reserve(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!cell_id_ok(c, v[i]) || !cell_id_ok(c, g[i]))
+      RET(TSW_EINVAL, "agent cell or goal off-grid or blocked (reference panics at agent.rs:358)");
+    goals.push_back(g[i]);
+  }
+  // one validation and one ensure_tables for all ticks: swaps permute the goals and rotations copy
+  // tick-start goals, so the goal set never grows; moves are next hops, so positions stay on free cells
+  TRY(ensure_tables(c, goals, true));
+  FleetLists S;
+  uint32_t* extra = nullptr;
+  TRY(fleet_lists_setup(c, n, radius, &S, fleet_apply_words(n), &extra));
+  FleetApplyArgs A{};
+  fleet_apply_layout(&A, extra, n);
+  A.v = S.v;
+  A.g = S.g;
+  const size_t stride = (size_t)ticks + 1;
+  if (v_rec || g_rec) {
+    TRY(fleet_grow(c, 2, ((v_rec ? 1 : 0) + (g_rec ? 1 : 0)) * (size_t)n * stride));
+    A.v_rec = v_rec ? c->d_fleet[2] : nullptr;
+    A.g_rec = g_rec ? c->d_fleet[2] + (v_rec ? (size_t)n * stride : 0) : nullptr;
+    A.rec_stride = ticks + 1;
+  }
+  std::memcpy(c->h_fleet, v, n * 4ull);
+  std::memcpy(c->h_fleet + n, g, n * 4ull);
+  HIPCHK(hipMemcpyAsync(S.v, c->h_fleet, 2ull * n * 4, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemsetAsync(A.changed, 0, 4, c->s));
+  // tick t stamps the changed word with t + 1; tick t + 1's count pass brings the word to the host in
+  // its own read-back, so a tick synchronises exactly as often as tsw_decide_fleet does
+  uint32_t t = 0, done = 0;
+  int rc = TSW_OK;
+  bool fixed = false;
+  for (; t < ticks; ++t) {
+    uint32_t chg = 0;
+    done = t;  // a tick that fails leaves the state after t ticks
+    if ((rc = fleet_lists_count(c, &S, A.changed, &chg)) != TSW_OK) break;
+    if (chg == FLEET_STUCK) {
+      c->err = "internal: the goal-op rounds made no progress";
+      rc = TSW_EHIP;
+      break;
+    }
+    if (t > 0 && chg != t) {  // tick t - 1 changed nothing: a fixed point, not counted
+      fixed = true;
+      break;
+    }
+    DecideDev D{};
+    uint32_t *d_poff, *d_pout;
+    if ((rc = fleet_decide_device(c, S, 0xFFFFFFFFu, &D, &d_poff, &d_pout)) != TSW_OK) break;
+    A.act = D.act;
+    A.cell = D.cell;
+    A.partner = D.par;
+    A.part_off = d_poff;
+    A.part = d_pout;
+    A.stamp = t + 1;
+    A.rec_col = t;
+    hipError_t e = launch_fleet_apply(A, c->s);
+    if (e != hipSuccess) {
+      c->err = std::string("launch_fleet_apply failed: ") + hipGetErrorString(e);
+      rc = TSW_EHIP;
+      break;
+    }
+  }
+  const uint32_t moves_run = t;  // ticks whose moves kernel ran (each wrote its own record column)
+  if (rc == TSW_OK && fixed) done = t - 1;
+  if (rc == TSW_OK && !fixed) {  // every tick ran: the last one's word has not been read yet
+    done = ticks;
+    if (ticks > 0) {
+      HIPCHK(hipMemcpyAsync(c->h_fleet, A.changed, 4, hipMemcpyDeviceToHost, c->s));
+      HIPCHK(hipStreamSynchronize(c->s));
+      if (c->h_fleet[0] == FLEET_STUCK) RET(TSW_EHIP, "internal: the goal-op rounds made no progress");
+      if (c->h_fleet[0] != ticks) done = ticks - 1;
+    }
+  }
+  rc = fleet_run_finish(c, rc, S, A, moves_run, done, ticks, v, g, v_rec, g_rec, ticks_done);
+  resolve_timing(c);
+  return rc;
+}
+
+int tsw_fleet_run(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n, uint32_t radius, uint32_t ticks, uint32_t* v_rec,
+                  uint32_t* g_rec, uint32_t* ticks_done) {
+  if (!c) return TSW_EINVAL;
+  NOT_FROM_RESOLVER(c);
+  if (!ticks_done) RET(TSW_EINVAL, "null argument");
+  *ticks_done = 0;
+  if (n == 0) return TSW_OK;
+  if (!v || !g) RET(TSW_EINVAL, "null argument");
+  TRY(set_device(c));
+  // a failed round may leave queued pairs PENDING: reset them before returning the error
+  return reset_pending_after(c, fleet_run_impl(c, v, g, n, radius, ticks, v_rec, g_rec, ticks_done));
 }
 
 int tsw_get_path_next(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, uint32_t k, uint32_t* next,

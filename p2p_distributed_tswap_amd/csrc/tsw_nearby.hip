@@ -21,54 +21,7 @@ namespace tsw {
 
 namespace {
 
-constexpr uint32_t NB_BLOCK = 256;                 // threads per workgroup, all kernels
-constexpr uint32_t NB_WAVES = NB_BLOCK / 64u;      // agents per workgroup of the wave-per-agent kernels
 constexpr uint32_t NB_ITEMS = NB_SCAN_TILE / NB_BLOCK;
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
-  return x;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, uint32_t lane) {
-#pragma unroll
-  for (uint32_t d = 1; d < 64u; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// block-wide sum of one value per thread (NB_BLOCK threads), valid in every thread
-__device__ __forceinline__ uint32_t block_sum(uint32_t x, uint32_t* sh /*NB_WAVES*/) {
-  x = wave_sum(x);
-  if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = x;
-  __syncthreads();
-  uint32_t t = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < NB_WAVES; ++w) t += sh[w];
-  __syncthreads();
-  return t;
-}
-
-// block-wide exclusive prefix of one value per thread; *total = the block's sum
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* sh /*NB_WAVES*/, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t incl = wave_incl_scan(x, lane);
-  if (lane == 63u) sh[wave] = incl;
-  __syncthreads();
-  uint32_t before = 0, t = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < NB_WAVES; ++w) {
-    const uint32_t sw = sh[w];
-    if (w < wave) before += sw;
-    t += sw;
-  }
-  __syncthreads();
-  *total = t;
-  return before + incl - x;
-}
 
 // ---- multi-block exclusive scan -------------------------------------------------------------------
 

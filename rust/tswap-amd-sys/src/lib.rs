@@ -165,6 +165,10 @@ extern "C" {
     pub fn tsw_decide_fleet(ctx: *mut TswCtx, v: *const u32, g: *const u32, n: u32, radius: u32, act: *mut u32,
                             cell: *mut u32, partner: *mut u32, part_off: *mut u32, part: *mut u32,
                             part_cap: u32) -> c_int;
+    pub fn tsw_fleet_apply(ctx: *mut TswCtx, v: *mut u32, g: *mut u32, n: u32, act: *const u32, cell: *const u32,
+                           partner: *const u32, part_off: *const u32, part: *const u32) -> c_int;
+    pub fn tsw_fleet_run(ctx: *mut TswCtx, v: *mut u32, g: *mut u32, n: u32, radius: u32, ticks: u32,
+                         v_rec: *mut u32, g_rec: *mut u32, ticks_done: *mut u32) -> c_int;
     pub fn tsw_dist_tables(ctx: *mut TswCtx, goals: *const u32, k: u32, out: *mut u16) -> c_int;
     pub fn tsw_dist_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_out: *mut u16) -> c_int;
     pub fn tsw_import_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_tables: *const u16) -> c_int;
@@ -509,6 +513,46 @@ impl Planner {
         self.check(rc)?;
         part.truncate(off[n] as usize);
         Ok((act, cell, partner, off, part))
+    }
+
+    /// One tick's decisions (decide_fleet's outputs, or the caller's own in that form) applied to v and g
+    /// in place, in the lock-step model of tswap.h: agents take their turns in ascending index, a goal
+    /// swap exchanges the current goals of requester and partner, a rotation hands participant m the
+    /// tick-start goal of participant m + 1.
+    #[allow(clippy::too_many_arguments)]
+    pub fn fleet_apply(&mut self, v: &mut [u32], g: &mut [u32], act: &[u32], cell: &[u32], partner: &[u32],
+                       part_off: &[u32], part: &[u32]) -> Result<(), TswapError> {
+        let n = v.len();
+        if g.len() != n || act.len() != n || cell.len() != n || partner.len() != n || part_off.len() != n + 1
+            || part_off.iter().any(|&o| o as usize > part.len()) {
+            return Err(TswapError { code: TSW_EINVAL, message: "fleet_apply: array lengths differ".into() });
+        }
+        self.check(unsafe {
+            tsw_fleet_apply(self.ctx, v.as_mut_ptr(), g.as_mut_ptr(), n as u32, act.as_ptr(), cell.as_ptr(),
+                            partner.as_ptr(), part_off.as_ptr(), part.as_ptr())
+        })
+    }
+
+    /// Up to `ticks` lock-step ticks with v and g resident on the device (tsw_fleet_run); stops early at
+    /// a fixed point. v and g are updated in place; returns (ticks_done, records): with `record` the
+    /// records are Some((v_rec, g_rec)), each n * (ticks + 1) words, agent-major, columns 0..=ticks_done
+    /// written.
+    #[allow(clippy::type_complexity)]
+    pub fn fleet_run(&mut self, v: &mut [u32], g: &mut [u32], radius: u32, ticks: u32, record: bool)
+                     -> Result<(u32, Option<(Vec<u32>, Vec<u32>)>), TswapError> {
+        let n = v.len();
+        if g.len() != n {
+            return Err(TswapError { code: TSW_EINVAL, message: "v and g lengths differ".into() });
+        }
+        let words = if record { n * (ticks as usize + 1) } else { 0 };
+        let (mut v_rec, mut g_rec) = (vec![0u32; words], vec![0u32; words]);
+        let (pv, pg) = if record { (v_rec.as_mut_ptr(), g_rec.as_mut_ptr()) }
+                       else { (std::ptr::null_mut(), std::ptr::null_mut()) };
+        let mut done = 0u32;
+        self.check(unsafe {
+            tsw_fleet_run(self.ctx, v.as_mut_ptr(), g.as_mut_ptr(), n as u32, radius, ticks, pv, pg, &mut done)
+        })?;
+        Ok((done, if record { Some((v_rec, g_rec)) } else { None }))
     }
 
     /// K1 distance tables (u16 per cell, TSW_DIST_INF blocked / unreachable), goal-major.
