@@ -823,7 +823,10 @@ WorkerCfg worker_config(const DevGrid& G, int num_cu, uint32_t n_agents, uint32_
   // CU's 160 KiB): every carve below must fit THAT, not the CU (C5's bitmap + heap
   // came to 160 KiB, 2 KiB over the dispatch's request, and no worker fit — exit mode)
   const size_t WAVE_LDS_MAX = std::min<size_t>(lds_cap, ::tsw::WAVE_LDS_MAX);
-  const size_t fbb = (size_t)G.H * G.Ww * 4u;
+  // the staged bitmap as coop_worker carves it: padded to 16 bytes, the detour bytes follow it. Unpadded
+  // (H * Ww not a multiple of 4, e.g. 200x130) a slice with an odd heap size came out 8 bytes short, and
+  // the last cells' detour bytes lay on the next worker's first heap entry
+  const size_t fbb = ((size_t)G.H * G.Ww * 4u + 15u) / 16u * 16u;
   const uint32_t want = hcap_want ? std::min(hcap_want, WAVE_HCAP) : WAVE_HCAP;
   // m: g-score placement; fb: free bitmap in LDS. With LDS g-scores the DAG early exit stages the
   // goal's detour bytes in LDS too (its reads then cost what a g-score read costs) and the heap gives
@@ -852,7 +855,9 @@ WorkerCfg worker_config(const DevGrid& G, int num_cu, uint32_t n_agents, uint32_
   const bool fits = force_gs == 0 || (force_gs == 1 && G.ncell <= WAVE_GS_LDS_MAX) ||
                     (force_gs == 2 && G.ncell <= WAVE_GB_LDS_MAX);
   if (force_gs >= 0 && fits) {  // A/B: another g-score placement than the default
-    WorkerCfg f = make((uint32_t)force_gs, true);
+    // forced global g-scores take TSW_WORKER_FB=0 too (on grids whose default keeps them in LDS the
+    // bitmap-less layout is reachable no other way)
+    WorkerCfg f = make((uint32_t)force_gs, force_gs != 0 || force_fb != 0);
     if (f.hcap >= 64u) return f;
   }
   WorkerCfg c = make(m, true);
