@@ -110,6 +110,7 @@ struct Tunables {
   int host_astar = -1;            // TSW_HOST_ASTAR: host A* service threads (0: off; -1: tsw_opts.host_astar)
   uint32_t host_delay_us = 0;     // TSW_HOST_ASTAR_DELAY_US (test knob): the host holds every reply back this long
   uint32_t host_ring = 0;         // TSW_HOST_ASTAR_RING (test knob): request / reply ring entries (0: HOST_RING_ENTRIES)
+  uint32_t host_early = 1;        // TSW_HOST_ASTAR_EARLY: urgent pairs asked of the host when queued (0: off; 2: and coop_wait leaves the host alone)
 
   static Tunables from_env() {
     Tunables t;
@@ -174,6 +175,7 @@ struct Tunables {
     t.host_astar = (int)num("TSW_HOST_ASTAR", 0, 16, -1);
     t.host_delay_us = (uint32_t)num("TSW_HOST_ASTAR_DELAY_US", 0, 1000000, 0);
     t.host_ring = (uint32_t)num("TSW_HOST_ASTAR_RING", 8, 1 << 14, 0);
+    t.host_early = (uint32_t)num("TSW_HOST_ASTAR_EARLY", 0, 2, t.host_early);
 #endif
     return t;
   }
@@ -286,6 +288,8 @@ struct tsw_ctx {
   uint32_t* h_hrep = nullptr;            // pinned, coherent, mapped: hring reply words
   uint32_t* d_hrep = nullptr;
   uint32_t hring = 0;
+  unsigned long long* d_hask = nullptr;  // early asks: two remembered request words per agent (PlanArgs::hask)
+  size_t haskcap = 0;                    // ... agents it holds
   uint32_t host_threads = 0;  // 0: service off
   std::vector<HostAstar> host_scratch;  // one per serving thread ([0]: the calling thread)
   std::atomic<uint64_t> host_queries{0}, host_busy_ns{0};
@@ -1659,6 +1663,19 @@ int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
   P.hreq = serve ? c->d_hreq : nullptr;
   P.hrep = serve ? c->d_hrep : nullptr;
   P.hring = serve ? c->hring : 0u;
+  P.hask = nullptr;
+  P.hearly = serve ? c->tun.host_early : 0u;
+  if (P.hearly && P.n) {
+    if (c->haskcap < P.n) {
+      HIPCHK(hipStreamSynchronize(c->s));
+      if (c->d_hask) (void)hipFree(c->d_hask);
+      c->d_hask = nullptr;
+      c->haskcap = 0;
+      HIPCHK(hipMalloc(&c->d_hask, (size_t)P.n * 2u * sizeof(unsigned long long)));
+      c->haskcap = P.n;
+    }
+    P.hask = c->d_hask;
+  }
   if (c->tun.plan_debug)
     fprintf(stderr, "[k_plan] planner LDS: agents %u part 0x%x flinks %u occ %u mu %u tasks %u (%zu B)\n", P.agents_lds,
             P.part_lds, P.f_lds, P.occ_lds, P.mu_lds, P.tasks_lds,
@@ -1670,6 +1687,8 @@ int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
     if (round > 16ull * P.n + 4096ull * (init.max_t + 1)) RET(TSW_EINVAL, "plan kernel made no progress");
     if (coop) {
       HIPCHK(hipMemsetAsync(c->d_cc, 0, sizeof(CoopCtl), c->s));
+      // tickets restart at 0 with every launch: no request word of an earlier one may match
+      if (P.hask) HIPCHK(hipMemsetAsync(c->d_hask, 0, (size_t)P.n * 2u * sizeof(unsigned long long), c->s));
       const uint32_t nt = P.mode == MODE_MAPD ? c->qt_count : 0u;
       if (nt) HIPCHK(hipMemcpyAsync(&c->d_cc->head_t, &c->qt_count, 4, hipMemcpyHostToDevice, c->s));
     }
@@ -1825,9 +1844,11 @@ int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
         if (coop) {
           const CoopCtl& cc = *c->h_cc;
           fprintf(stderr, "[k_plan] needed pairs unresolved (never queued / queued speculatively): PRE1 %u/%u RULES %u/%u "
-                  "MOVE %u/%u | PRE1 never queued: assigned %u, picked up %u | chain queries %llu of %llu\n", cc.dbg_need[0], cc.dbg_need[1], cc.dbg_need[2],
+                  "MOVE %u/%u | PRE1 never queued: assigned %u, picked up %u | chain queries %llu of %llu | host asked %u (early %u) "
+                  "used %u (early, in refresh %u)\n", cc.dbg_need[0], cc.dbg_need[1], cc.dbg_need[2],
                   cc.dbg_need[3], cc.dbg_need[4], cc.dbg_need[5], cc.dbg_need[6], cc.dbg_need[7],
-                  (unsigned long long)cc.chain_queries, (unsigned long long)cc.worker_queries);
+                  (unsigned long long)cc.chain_queries, (unsigned long long)cc.worker_queries, cc.host_asked, cc.early_asked,
+                  cc.host_used, cc.early_taken);
           {
             static const char* nm[6] = {"r3b", "r3s", "rot", "mv", "asg", "pick"};
             std::string line = "[k_plan] PRE1 unresolved by agent change (unknown/pending):";
@@ -2297,7 +2318,7 @@ void tsw_destroy(tsw_ctx* c) {
   if (c->h_dups) (void)hipHostFree(c->h_dups);
   fre(c->d_task); fre(c->d_occ); fre(c->d_nhc); fre(c->d_ctl); fre(c->d_pargs); fre(c->d_ticks); fre(c->d_dtag); fre(c->d_live); fre(c->d_klt); fre(c->d_kpos); fre(c->d_kbox); fre(c->d_kcnt); fre(c->d_pick); fre(c->d_dlv); fre(c->d_unused);
   fre(c->d_rec); fre(c->d_grec); fre(c->d_tmp_a); fre(c->d_tmp_b); fre(c->d_fleet[0]); fre(c->d_fleet[1]); fre(c->d_fleet[2]);
-  fre(c->d_cc); fre(c->d_QS); fre(c->d_QT); fre(c->d_QH); fre(c->d_QP); fre(c->d_pred); fre(c->d_wf); fre(c->d_govf); fre(c->d_mg_grp); fre(c->d_mg_wl); fre(c->d_mg_anch);
+  fre(c->d_cc); fre(c->d_QS); fre(c->d_QT); fre(c->d_QH); fre(c->d_QP); fre(c->d_pred); fre(c->d_wf); fre(c->d_hask); fre(c->d_govf); fre(c->d_mg_grp); fre(c->d_mg_wl); fre(c->d_mg_anch);
   if (c->h_cc) (void)hipHostFree(c->h_cc);
   if (c->h_flags) (void)hipHostFree(c->h_flags);
   if (c->h_hreq) (void)hipHostFree(c->h_hreq);

@@ -112,6 +112,8 @@ struct CoopCtl {
   // predicted task chains: jobs run, and (TSW_PLAN_DEBUG) assignments whose task was the agent's last prediction
   uint32_t pred_jobs, pred_asg, pred_hit, pred_none;
   uint32_t host_asked, host_used;  // host A* service: pairs the planner asked the host for / codes it took from a reply
+  // ... of which asked a step early, when the pair was queued as urgent / taken by refresh_codes without a wait
+  uint32_t early_asked, early_taken;
 };
 
 struct AstarQuery {

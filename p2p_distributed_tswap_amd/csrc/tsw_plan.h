@@ -1,10 +1,57 @@
 // tsw_plan.h — arguments and resumable control block of the persistent plan kernel.
 #pragma once
-#include <hip/hip_runtime.h>
-
 #include <cstddef>
 
 #include "tsw_internal.h"
+
+// The host A* request ring's word layout and match test are plain C++ (tests/host/host_ask_match_main.cpp
+// builds them with the host compiler alone); everything below them needs HIP.
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define TSW_RING_HD __host__ __device__ __forceinline__
+#else
+#define TSW_RING_HD inline
+#endif
+
+namespace tsw {
+
+// ---- host A* service: request words (PlanArgs::hreq / hrep / hask) ----------------------------
+constexpr uint32_t HOST_RING_MAX_TICKETS = 0xFFFFF0u;  // seq fits 24 bits (hrep keeps 8 for the code)
+
+// The request word of ticket t for the pair (v, goal): seq << 40 | v << 20 | goal with seq = t + 1, so a
+// zeroed word is no request (cells < 2^20).
+TSW_RING_HD unsigned long long host_req_word(uint32_t ticket, uint32_t v, uint32_t goal) {
+  return ((unsigned long long)(ticket + 1u) << 40) | ((unsigned long long)v << 20) | (unsigned long long)goal;
+}
+
+// Is the remembered request word w an outstanding request for (v, goal)? `tickets` = tickets taken so far
+// this launch, `ring` = ring entries. False for a zeroed word, a word for another pair, a ticket not taken
+// yet, and a ticket older than the ring window (ticket t's slot belongs to ticket t + ring once that is
+// taken). *ticket (if given) receives the word's ticket.
+TSW_RING_HD bool host_req_live(unsigned long long w, uint32_t v, uint32_t goal, uint32_t tickets, uint32_t ring,
+                               uint32_t* ticket = nullptr) {
+  const uint32_t seq = (uint32_t)(w >> 40);
+  if (seq == 0u || seq > tickets || seq > HOST_RING_MAX_TICKETS || tickets - (seq - 1u) > ring) return false;
+  if ((w & 0xFFFFFFFFFFull) != (((unsigned long long)v << 20) | (unsigned long long)goal)) return false;
+  if (ticket) *ticket = seq - 1u;
+  return true;
+}
+
+// Does the reply word r (seq << 8 | code, read from the slot of w's ticket) answer the pair (v, goal) the
+// remembered request word w asked for? True only when w is live for (v, goal) (host_req_live), r carries
+// w's seq — not that of a ticket that reused the slot after the ring wrapped, nor zero — and a code
+// <= NH_STAY, which *code then receives.
+TSW_RING_HD bool host_reply_match(unsigned long long w, uint32_t r, uint32_t v, uint32_t goal, uint32_t tickets,
+                                  uint32_t ring, uint8_t* code) {
+  if (!host_req_live(w, v, goal, tickets, ring)) return false;
+  if ((r >> 8) != (uint32_t)(w >> 40) || (r & 0xFFu) > NH_STAY) return false;
+  *code = (uint8_t)(r & 0xFFu);
+  return true;
+}
+
+}  // namespace tsw
+
+#if defined(__HIPCC__)
 
 namespace tsw {
 
@@ -137,8 +184,16 @@ struct PlanArgs {
   unsigned long long* hreq;
   uint32_t* hrep;
   uint32_t hring;
+  // early asks (round 9): a pair the walk-ahead queues as urgent is put on the request ring at once, a
+  // step before its code is read, and its request word is remembered per agent — hask[2k]: the
+  // walk-ahead pair, hask[2k + 1]: the pickup-arrival pair (zeroed per launch; nullptr: off).
+  // refresh_codes takes the reply when it finds the agent's code unresolved, coop_wait spins on the
+  // remembered ticket instead of asking again (host_req_live / host_reply_match above).
+  // hearly: TSW_HOST_ASTAR_EARLY (1; 2 = diagnostic: coop_wait neither asks nor polls the host, so
+  // every host code taken came through refresh_codes).
+  unsigned long long* hask;
+  uint32_t hearly;
 };
-constexpr uint32_t HOST_RING_MAX_TICKETS = 0xFFFFF0u;  // seq fits 24 bits (hrep keeps 8 for the code)
 
 // Agent arrays that go to LDS one by one when all of them do not fit (PlanArgs::part_lds), in the
 // order the host admits them: the rules phase's successor chains and labels first (its relabel walks
@@ -219,3 +274,5 @@ hipError_t launch_plan(const PlanArgs& P, PlanArgs* d_args, const WorkerArgs* W,
                        uint32_t block, hipStream_t s);
 
 }  // namespace tsw
+
+#endif  // __HIPCC__

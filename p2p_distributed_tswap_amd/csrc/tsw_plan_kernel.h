@@ -400,6 +400,67 @@ __device__ __forceinline__ void prefetch_pair(const PlanArgs& P, uint32_t v, uin
   put_query(P, p, cur, v, g, tab);
 }
 
+// ---- host A* service, early asks (PlanArgs::hask; round 9) -------------------------------------
+// A pair queued as urgent is read one step later; a worker wave needs ~0.85 ms for its A*, the host
+// ~35 us. So the pair goes on the host request ring now, by coop_wait's protocol — a ticket from
+// s_q[10] against the room limit s_q[11], one 64-bit system-scope store — and its request word is
+// remembered in the agent's slot. Nothing is asked when the slot already holds the pair under a ticket
+// inside the ring window (a blocked agent does not re-ask every step) or when the ring has no room.
+// The room limit is the host's tail word + ring size; the tail only grows, so a stale limit is a safe
+// lower bound and the system-scope load that refreshes it runs only when the tickets have reached it.
+__device__ __noinline__ void host_ask_early(const PlanArgs& P, uint32_t* s_q, uint32_t v, uint32_t g,
+                                            unsigned long long* slot) {
+  uint32_t cur = *(volatile uint32_t*)&s_q[10];
+  if (host_req_live(*slot, v, g, cur, P.hring)) return;
+  uint32_t lim = *(volatile uint32_t*)&s_q[11];
+  if (cur >= lim) {
+    lim = min(__hip_atomic_load(&P.hflags[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) + P.hring,
+              HOST_RING_MAX_TICKETS);
+    atomicMax(&s_q[11], lim);
+  }
+  for (;;) {
+    if (cur >= lim) return;  // the ring is full: not asked
+    const uint32_t prev = atomicCAS(&s_q[10], cur, cur + 1u);
+    if (prev == cur) break;
+    cur = prev;
+  }
+  const unsigned long long w = host_req_word(cur, v, g);
+  __hip_atomic_store(&P.hreq[cur & (P.hring - 1u)], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  *slot = w;
+  atomicAdd(&P.cc->host_asked, 1u);
+  atomicAdd(&P.cc->early_asked, 1u);
+}
+
+// The ticket of an outstanding early ask for agent k's pair (v, g), else ~0.
+__device__ __forceinline__ uint32_t host_early_ticket(const PlanArgs& P, const uint32_t* s_q, uint32_t k, uint32_t v,
+                                                      uint32_t g) {
+  const uint32_t tickets = *(volatile const uint32_t*)&s_q[10];
+  uint32_t t = 0xFFFFFFFFu;
+  if (!host_req_live(P.hask[2u * k], v, g, tickets, P.hring, &t)) host_req_live(P.hask[2u * k + 1u], v, g, tickets, P.hring, &t);
+  return t;
+}
+
+// refresh_codes found agent k's code unresolved: if an early ask for its pair (v, g) has been answered,
+// publish the code as coop_wait does (relaxed agent-scope byte store into the table store) and return
+// the code, else NH_UNKNOWN. Never waits: a missing, late or foreign reply is no reply.
+__device__ __noinline__ uint8_t host_take_early(const PlanArgs& P, const uint32_t* s_q, uint32_t k, uint32_t v, uint32_t g,
+                                                int32_t tab) {
+  const uint32_t tickets = *(volatile const uint32_t*)&s_q[10];
+  for (uint32_t j = 0; j < 2u; ++j) {
+    const unsigned long long w = P.hask[2u * k + j];
+    uint32_t t;
+    if (!host_req_live(w, v, g, tickets, P.hring, &t)) continue;
+    const uint32_t r = __hip_atomic_load(&P.hrep[t & (P.hring - 1u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    uint8_t code;
+    if (!host_reply_match(w, r, v, g, tickets, P.hring, &code)) continue;
+    __hip_atomic_store(P.nh + (uint64_t)tab * P.nstride + v, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    atomicAdd(&P.cc->host_used, 1u);
+    atomicAdd(&P.cc->early_taken, 1u);
+    return code;
+  }
+  return NH_UNKNOWN;
+}
+
 // parallel: refresh next-hop codes of agents whose code is dirty; unresolved pairs are
 // appended to the launch's K3 queue (s_q counts every pair queued since the launch began,
 // speculative prefetches included). Returns how many dirty agents still lack a code
@@ -419,8 +480,11 @@ __device__ uint32_t refresh_codes(const PlanArgs& P, const Arrays& S, uint32_t* 
       continue;
     }
     const uint8_t code = nh_code(P, tab, v);
-    if (code <= NH_STAY) {
-      S.NHC[k] = code;
+    // unresolved: the host may have answered an early ask for this pair a step ago (the slots are read
+    // only here, so a resolved step pays nothing); the agent then does not count as needing
+    const uint8_t hcode = (code > NH_STAY && P.hask) ? host_take_early(P, s_q, k, v, g, tab) : code;
+    if (hcode <= NH_STAY) {
+      S.NHC[k] = hcode;
     } else {
       if (PLAN_DBG && P.coop && (code == NH_UNKNOWN || code == NH_PENDING_S)) {
         const uint32_t grp = sec == SEC_PRE1 ? 0u : sec == SEC_RULES ? 1u : 2u;
@@ -524,15 +588,21 @@ __device__ int coop_wait(const PlanArgs& P, const Arrays& S, uint32_t* s_q, uint
   // not queued leaves the loop at its first read and is not asked (asking for every dirty agent kept one
   // host core busy with pairs nobody waited for). hmask: bit j = the thread's j-th dirty agent was asked
   // (the first 32 of them), its ticket is hbase + the number of asked ones before it.
-  uint32_t hbase = 0, hmask = 0;
-  if (P.hring) {
+  // A pair with an outstanding early ask (host_ask_early) takes no new ticket — the host runs one A* per
+  // pair: emask marks it and the loop below spins on the remembered ticket's reply slot. hearly == 2
+  // (diagnostic): nothing is asked or polled here.
+  uint32_t hbase = 0, hmask = 0, emask = 0;
+  if (P.hring && P.hearly != 2u) {
     uint32_t j = 0;
     for (uint32_t k = tid; k < P.n && j < 32u; k += bd) {
       if (S.NHC[k] <= NH_STAY || S.V[k] == S.G[k] || S.GT[k] < 0) continue;
       const uint8_t* p = P.nh + (uint64_t)S.GT[k] * P.nstride + S.V[k];
       const uint8_t c = (uint8_t)(ld_agent(reinterpret_cast<const uint32_t*>((uintptr_t)p & ~(uintptr_t)3u)) >>
                                   (8u * (uint32_t)((uintptr_t)p & 3u)));
-      if (c == NH_PENDING || c == NH_PENDING_S) hmask |= 1u << j;
+      if (c == NH_PENDING || c == NH_PENDING_S) {
+        if (P.hask && host_early_ticket(P, s_q, k, S.V[k], S.G[k]) != 0xFFFFFFFFu) emask |= 1u << j;
+        else hmask |= 1u << j;
+      }
       ++j;
     }
     if (hmask) {
@@ -556,9 +626,8 @@ __device__ int coop_wait(const PlanArgs& P, const Arrays& S, uint32_t* s_q, uint
       for (uint32_t k = tid; k < P.n && j < 32u; k += bd) {
         if (S.NHC[k] <= NH_STAY || S.V[k] == S.G[k] || S.GT[k] < 0) continue;
         if ((hmask >> j) & 1u) {
-          __hip_atomic_store(&P.hreq[t & (P.hring - 1u)],
-                             ((unsigned long long)(t + 1u) << 40) | ((unsigned long long)S.V[k] << 20) | S.G[k],
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(&P.hreq[t & (P.hring - 1u)], host_req_word(t, S.V[k], S.G[k]), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_SYSTEM);
           ++t;
         }
         ++j;
@@ -572,10 +641,16 @@ __device__ int coop_wait(const PlanArgs& P, const Arrays& S, uint32_t* s_q, uint
     if (S.NHC[k] <= NH_STAY) continue;
     const uint32_t v = S.V[k];
     const int32_t tab = S.GT[k];
-    if (v == S.G[k] || tab < 0) continue;
-    const bool asked = hj < 32u && ((hmask >> hj) & 1u);
-    const uint32_t tk = hbase + (uint32_t)__builtin_popcount(hmask & ((1u << (hj & 31u)) - 1u));  // its ticket, if asked
+    const uint32_t gk = S.G[k];
+    if (v == gk || tab < 0) continue;
+    bool asked = hj < 32u && ((hmask >> hj) & 1u);
+    uint32_t tk = hbase + (uint32_t)__builtin_popcount(hmask & ((1u << (hj & 31u)) - 1u));  // its ticket, if asked
+    if (hj < 32u && ((emask >> hj) & 1u)) {  // asked early: that ticket (gone from its window meanwhile: not polled)
+      tk = host_early_ticket(P, s_q, k, v, gk);
+      asked = tk != 0xFFFFFFFFu;
+    }
     ++hj;
+    const unsigned long long hw = host_req_word(tk, v, gk);
     const uint8_t* p = P.nh + (uint64_t)tab * P.nstride + v;
     const uint32_t* w = reinterpret_cast<const uint32_t*>((uintptr_t)p & ~(uintptr_t)3u);
     const uint32_t sh = 8u * (uint32_t)((uintptr_t)p & 3u);
@@ -589,9 +664,10 @@ __device__ int coop_wait(const PlanArgs& P, const Arrays& S, uint32_t* s_q, uint
       if (asked) {
         // the host's reply for this ticket (another seq: an older or no reply): publish the code as a worker does
         const uint32_t r = __hip_atomic_load(&P.hrep[tk & (P.hring - 1u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if ((r >> 8) == tk + 1u && (r & 0xFFu) <= NH_STAY) {
-          __hip_atomic_store(const_cast<uint8_t*>(p), (uint8_t)(r & 0xFFu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          S.NHC[k] = (uint8_t)(r & 0xFFu);
+        uint8_t hc;
+        if (host_reply_match(hw, r, v, gk, *(volatile uint32_t*)&s_q[10], P.hring, &hc)) {
+          __hip_atomic_store(const_cast<uint8_t*>(p), hc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          S.NHC[k] = hc;
           atomicAdd(&P.cc->host_used, 1u);
           break;
         }
@@ -699,7 +775,7 @@ __device__ void rules_prefetch(const PlanArgs& P, const Arrays& S, uint32_t* s_q
 // only their goals, hence their next hops and successors, moved, so only their pairs are new.
 // After rules_init (SUCC valid).
 __device__ uint32_t walk_prefetch(const PlanArgs& P, uint32_t* s_q, uint32_t u, uint32_t g, int32_t tab,
-                                  uint32_t hops, uint32_t h0 = 0u, uint32_t* end = nullptr,
+                                  uint32_t hops, unsigned long long* hslot, uint32_t h0 = 0u, uint32_t* end = nullptr,
                                   uint32_t* endh = nullptr);
 __device__ void dag_prefetch(const PlanArgs& P, uint32_t* s_q, uint32_t u, uint32_t g, int32_t tab);
 
@@ -730,7 +806,9 @@ __device__ __forceinline__ void prefetch_changed(const PlanArgs& P, const Arrays
   if (S.V[k] != S.G[k] && (P.prefetch_ext & 4u)) {
     // the agent's new path: walked ahead (and the DAG past its first unresolved cell) now, a step
     // before the next step's walk-ahead would queue it
-    if (c < NH_STAY) walk_prefetch(P, s_q, step_cell(S.V[k], c, P.W), S.G[k], tab, P.wide_prefetch ? P.wide_prefetch : 1u);
+    if (c < NH_STAY)
+      walk_prefetch(P, s_q, step_cell(S.V[k], c, P.W), S.G[k], tab, P.wide_prefetch ? P.wide_prefetch : 1u,
+                    P.hask ? P.hask + 2u * k : nullptr);
     else if (c > NH_STAY && P.dag_prefetch) dag_prefetch(P, s_q, S.V[k], S.G[k], tab);
   } else if (c < NH_STAY && S.V[k] != S.G[k]) {
     const uint32_t u = step_cell(S.V[k], c, P.W);
@@ -806,8 +884,10 @@ __device__ void dag_prefetch(const PlanArgs& P, uint32_t* s_q, uint32_t u, uint3
 // Walk the resolved codes toward g from cell u, which lies h0 resolved hops past the agent's next cell,
 // until hop `hops`; queue the first unresolved pair (and the DAG past it). Returns the hops left when the
 // walk reached g, else 0. *end / *endh (if given): the cell the walk stopped at and its hop index.
+// hslot: the walking agent's early-ask slot (PlanArgs::hask) — an urgent pair is then also asked of the host
+// now (host_ask_early) — or nullptr where the walk is no agent's own path or early asks are off.
 __device__ uint32_t walk_prefetch(const PlanArgs& P, uint32_t* s_q, uint32_t u, uint32_t g, int32_t tab,
-                                  uint32_t hops, uint32_t h0, uint32_t* end, uint32_t* endh) {
+                                  uint32_t hops, unsigned long long* hslot, uint32_t h0, uint32_t* end, uint32_t* endh) {
   uint32_t h = h0;
   uint32_t left = 0;
   for (; h < hops; ++h) {
@@ -819,8 +899,10 @@ __device__ uint32_t walk_prefetch(const PlanArgs& P, uint32_t* s_q, uint32_t u, 
     if (cu == NH_UNKNOWN || cu == NH_PENDING || cu == NH_PENDING_S) {
       // a pair the agent reads within urgent_hops steps goes to the needed queue (served before the
       // speculative backlog, which on wh10k holds ~500 pairs when a wait starts); farther ones are speculative
-      if (P.coop && h < P.urgent_hops) urgent_pair(P, u, g, tab, s_q, cu);
-      else if (cu == NH_UNKNOWN) prefetch_pair(P, u, g, tab, s_q);
+      if (P.coop && h < P.urgent_hops) {
+        urgent_pair(P, u, g, tab, s_q, cu);
+        if (hslot) host_ask_early(P, s_q, u, g, hslot);
+      } else if (cu == NH_UNKNOWN) prefetch_pair(P, u, g, tab, s_q);
       if (P.dag_prefetch) dag_prefetch(P, s_q, u, g, tab);
       break;
     }
@@ -864,8 +946,10 @@ __device__ void nextnext_prefetch(const PlanArgs& P, const Arrays& S, uint32_t* 
           const uint32_t vx = vk % W, vy = vk / W, px = pc % W, py = pc / W;
           const uint32_t man = (vx > px ? vx - px : px - vx) + (vy > py ? vy - py : py - vy);
           // arriving within urgent_hops + 1 steps (Manhattan bounds the path from below): needed queue
-          if (P.coop && man <= P.urgent_hops + 1u && (cp == NH_UNKNOWN || cp == NH_PENDING_S)) urgent_pair(P, pc, dc, dt, s_q, cp);
-          else if (cp == NH_UNKNOWN) prefetch_pair(P, pc, dc, dt, s_q);
+          if (P.coop && man <= P.urgent_hops + 1u && (cp == NH_UNKNOWN || cp == NH_PENDING_S)) {
+            urgent_pair(P, pc, dc, dt, s_q, cp);
+            if (P.hask) host_ask_early(P, s_q, pc, dc, P.hask + 2u * k + 1u);
+          } else if (cp == NH_UNKNOWN) prefetch_pair(P, pc, dc, dt, s_q);
         }
       }
     }
@@ -898,9 +982,10 @@ __device__ void nextnext_prefetch(const PlanArgs& P, const Arrays& S, uint32_t* 
       }
     }
     uint32_t ue = u0, he = h0;
-    const uint32_t left = h0 >= hops ? 0u : walk_prefetch(P, s_q, u0, gk, tab, hops, h0, &ue, &he);
+    const uint32_t left =
+        h0 >= hops ? 0u : walk_prefetch(P, s_q, u0, gk, tab, hops, P.hask ? P.hask + 2u * k : nullptr, h0, &ue, &he);
     if (P.wf) P.wf[k] = make_uint4(vk, gk, ue, he);
-    if (left > 0u && dtab >= 0 && (P.prefetch_ext & 2u)) walk_prefetch(P, s_q, pc, dc, dtab, left);
+    if (left > 0u && dtab >= 0 && (P.prefetch_ext & 2u)) walk_prefetch(P, s_q, pc, dc, dtab, left, nullptr);
   }
   PBAR();
 }
@@ -1135,7 +1220,7 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
     s_q[8] = 0;  // predicted task chains queued this launch (coop mode)
     s_q[9] = 0;  // ... last published head
     s_q[10] = 0;  // host A* service: request tickets taken this launch
-    s_q[11] = 0;  // ... tickets below this fit the ring (claimed by the host + ring size, read at each wait)
+    s_q[11] = 0;  // ... tickets below this fit the ring (claimed by the host + ring size: read at each wait, and by an early ask that reaches it)
     if (P.coop) __hip_atomic_store(&P.cc->t_now, s_ctl.t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int k = 0; k < 48; ++k) s_tick[k] = 0;
     bar_ids()[16] = 0u;
