@@ -79,6 +79,7 @@ struct Tunables {
   uint32_t chain_hops = 0;        // TSW_CHAIN_HOPS: hops resolved per task chain (0: the whole path)
   uint32_t move_round0 = 0;       // TSW_MOVE_ROUND0 (test knob): movement-round counter at the plan start (forces the MU32 tag wrap)
   bool walk_cache = true;         // TSW_WALK_CACHE=0: the step-start walk-ahead re-reads every code from the agent's next cell
+  uint32_t walk_step = 4;         // TSW_WALK_STEP: new hops a step-start walk reads past its cached frontier per timestep (0: no budget, the whole depth at once; round 10, profiles/r10/walk_step_sweep.txt)
   uint32_t predict = 1;           // TSW_PREDICT: predicted task chains, bit 0 at pickups, bit 1 at delivery-goal changes (0: off)
   uint32_t urgent_hops = 1;       // TSW_URGENT_HOPS: walk-ahead pairs this close are queued as needed (0: off)
   uint32_t dag_width = 4;         // TSW_DAG_WIDTH: cells per DAG prefetch level (<= 16)
@@ -148,6 +149,7 @@ struct Tunables {
     t.hot_chains = num("TSW_HOT_CHAINS", 0, 1, t.hot_chains ? 1 : 0) != 0;
     t.predict = (uint32_t)num("TSW_PREDICT", 0, 3, t.predict);
     t.walk_cache = num("TSW_WALK_CACHE", 0, 1, 1) != 0;
+    t.walk_step = (uint32_t)num("TSW_WALK_STEP", 0, 1 << 16, t.walk_step);
     t.move_round0 = (uint32_t)num("TSW_MOVE_ROUND0", 0, 0x7FFFFFFF, 0);
     t.ab_flags = (uint32_t)num("TSW_AB_FLAGS", 0, 255, t.ab_flags);
     t.t0_delay_us = (uint32_t)num("TSW_T0_DELAY_US", 0, 10000000, t.t0_delay_us);
@@ -1423,6 +1425,8 @@ PlanArgs plan_args(tsw_ctx* c, uint32_t n, uint32_t m, uint32_t mode, bool want_
     if (c->d_dtag && hipMemsetAsync(c->d_dtag, 0, (size_t)n * 4, c->s) == hipSuccess) P.dtag = c->d_dtag;
   }
   P.wf = nullptr;
+  // the frontier is re-armed per call, so a tsw_step call (one timestep) could never carry a budgeted walk on
+  P.walk_step = mode == MODE_STEP ? 0u : c->tun.walk_step;
   if (c->tun.walk_cache && n) {  // re-armed per plan / step call (a goal never matches 0xFFFFFFFF)
     if (c->wfcap < n) {
       if (c->d_wf) (void)hipFree(c->d_wf);

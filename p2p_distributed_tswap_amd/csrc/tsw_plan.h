@@ -193,6 +193,8 @@ struct PlanArgs {
   // every host code taken came through refresh_codes).
   unsigned long long* hask;
   uint32_t hearly;
+  // new hops a step-start walk reads past its cached frontier (wf) per timestep (0: no budget, the whole depth)
+  uint32_t walk_step;
 };
 
 // Agent arrays that go to LDS one by one when all of them do not fit (PlanArgs::part_lds), in the

@@ -981,9 +981,14 @@ __device__ void nextnext_prefetch(const PlanArgs& P, const Arrays& S, uint32_t* 
         }
       }
     }
+    // A hop budget per step (round 10): the walk reads at most walk_step hops past its cached frontier and goes
+    // on next step, up to the same depth; the agent moves one hop per step, so the frontier gains walk_step - 1.
+    // The delivery-leg continuation below is not cached, so it gets what is left of this step's budget: at most
+    // walk_step hops past the pickup (the workers' task chains resolve that leg as well).
     uint32_t ue = u0, he = h0;
+    const uint32_t hlim = (P.walk_step && P.wf) ? min(hops, h0 + P.walk_step) : hops;
     const uint32_t left =
-        h0 >= hops ? 0u : walk_prefetch(P, s_q, u0, gk, tab, hops, P.hask ? P.hask + 2u * k : nullptr, h0, &ue, &he);
+        h0 >= hops ? 0u : walk_prefetch(P, s_q, u0, gk, tab, hlim, P.hask ? P.hask + 2u * k : nullptr, h0, &ue, &he);
     if (P.wf) P.wf[k] = make_uint4(vk, gk, ue, he);
     if (left > 0u && dtab >= 0 && (P.prefetch_ext & 2u)) walk_prefetch(P, s_q, pc, dc, dtab, left, nullptr);
   }
