@@ -66,8 +66,8 @@ extern "C" {
  * tsw_plan_mapd_resolved resolver (TSW_EINVAL); 6: tsw_stats coop_worker_queries / coop_worker_pops;
  * 7: tsw_opts.reserved became host_astar, tsw_stats gained host_astar_queries / host_astar_used /
  * host_astar_ms, tsw_host_next_hop_codes; 8: tsw_nearby, tsw_decide_fleet. Still 8: tsw_fleet_apply and
- * tsw_fleet_run were added without touching a struct or an existing signature; a caller that wants
- * them looks the two symbols up (dlsym) instead of comparing the revision. */
+ * tsw_fleet_run, and after them tsw_fleet_mapd, were added without touching a struct or an existing
+ * signature; a caller that wants them looks the symbols up (dlsym) instead of comparing the revision. */
 #define TSW_ABI_VERSION 8
 
 /* AgentState discriminants in declaration order (src/map/agent.rs:9-15) */
@@ -273,7 +273,8 @@ int tsw_decide_fleet(tsw_ctx *ctx, const uint32_t *v, const uint32_t *g, uint32_
  *   TSW_ACT_WAIT                  nothing.
  * Every other v1[i] = v0[i]; g1 = G. Left out — the caller's business between calls: the agent's
  * bookkeeping (pending_goal_swap is always cleared within the tick; pending_rotation is never cleared
- * in the reference), task_state, my_task and the pickup / delivery hand-over.
+ * in the reference), task_state, my_task and the pickup / delivery hand-over (tsw_fleet_mapd, below,
+ * runs the tick with a task phase of this library's own).
  *
  * tsw_fleet_apply: one tick's decisions, in tsw_decide_fleet's output form (they may be the caller's
  * own), applied to v and g in place with exactly the sequential semantics above. TSW_EINVAL with v and g
@@ -299,6 +300,54 @@ int tsw_fleet_apply(tsw_ctx *ctx, uint32_t *v, uint32_t *g, uint32_t n,
  * positions on free cells (moves are next hops): the inputs are validated once for all ticks. */
 int tsw_fleet_run(tsw_ctx *ctx, uint32_t *v, uint32_t *g, uint32_t n, uint32_t radius, uint32_t ticks,
                   uint32_t *v_rec, uint32_t *g_rec, uint32_t *ticks_done);
+
+/* A MAPD run on the lock-step tick, resident on the device: tsw_plan_mapd's inputs and record layout,
+ * the decentralized mode's movement. The model is this library's own composition of three pieces of the
+ * reference, because the reference's decentralized hand-over cannot be reproduced: agent.rs:859-888 keys
+ * pickup / delivery on the agent's OWN task cells, not on the goal it currently heads for, so after the
+ * first goal swap or rotation the agent walks to another agent's goal, arrives at neither of its own
+ * cells and its timer branch (:840) goes quiet for good; and task_state, once WaitingForGoalSwap /
+ * WaitingForRotation (:904, :919), is never set back. Literally reproduced, the fleet freezes after its
+ * first swap. Modelled instead:
+ *   - the state and task management of tswap_mapd (algorithm/tswap.rs:106-121), keyed on v == g whatever
+ *     goal the agent holds at the moment — the rule tsw_plan_mapd implements;
+ *   - the dispatch of the decentralized manager (bin/decentralized/manager.rs:275-300, :526-551): an agent
+ *     without a task gets the NEXT task of the stream; there is no nearest-pickup search;
+ *   - the lock-step tick defined above tsw_fleet_apply.
+ * State per agent i: v[i], g[i] (cell ids), st[i] in {IDLE, TO_PICKUP, TO_DELIVERY}, tk[i] (task index or
+ * 0xFFFFFFFF); one counter `next`, the number of tasks handed out. Start: v[i] = g[i] = cell(starts[i]),
+ * st = IDLE, tk = none, next = 0, t = 0. Then repeat:
+ *   1. Task phase, for i = 0 .. n-1 in ascending index (tswap.rs:106-139 with the manager's dispatch in
+ *      place of :125-131). If v[i] == g[i]: TO_PICKUP becomes TO_DELIVERY with g[i] =
+ *      cell(tasks[tk[i]].delivery); TO_DELIVERY becomes IDLE with tk[i] = none. Then, if st[i] == IDLE and
+ *      next < m: tk[i] = next, st[i] = TO_PICKUP, g[i] = cell(tasks[next].pickup), next += 1. An agent
+ *      that goes idle takes a task in the same step; one just given a task is not checked for arrival
+ *      again in that step.
+ *   2. The tick: exactly one tick of the lock-step model on (v, g) with `radius` (tsw_decide_fleet followed
+ *      by tsw_fleet_apply).
+ *   3. Ending. done = (next == m and every st[i] == IDLE); unchanged = (stage 1 made no transition and the
+ *      tick changed neither v nor g). If done: record column t, t += 1, end with *stalled = 0 — even when
+ *      the step changed nothing, so m == 0 gives one column, as tswap_mapd does. Else if unchanged: a step
+ *      is a pure function of the state, nothing will ever change again: end with *stalled = 1, this step is
+ *      not recorded. Else: record column t, t += 1, and end with *stalled = 0 if t > max_t (tswap.rs:167).
+ *   4. Record (tswap.rs:144-158): column t of agent i holds (x, y) of v[i] and the state TSW_IDLE for IDLE,
+ *      TSW_PICKING for TO_PICKUP, and for TO_DELIVERY TSW_DELIVERED if v[i] == g[i], else TSW_CARRYING;
+ *      g[i] in goal_out and tk[i] in task_out where those are given.
+ * out, goal_out, task_out: agent-major, n * (max_t + 1) each, like tsw_plan_mapd_trace's; goal_out and
+ * task_out may be NULL. Columns 0 .. *out_T - 1 are written, later columns are left untouched. stalled may
+ * be NULL. TSW_EINVAL before anything is launched: a start off-grid or blocked; ANY task cell off-grid or
+ * blocked — all m tasks are checked up front, dispatched or not: unlike tsw_plan_mapd there is no reference
+ * panic site to imitate; max_t > 2^20; a NULL out_T, or a NULL out with n > 0. Duplicate starts are legal,
+ * as everywhere in the fleet entry points. n == 0: TSW_OK, *out_T = 0, *stalled = 0. A step that fails
+ * (tsw_fleet_run's codes: TSW_EOVERFLOW from the list limits, TSW_ENOMEM, TSW_EHIP) returns its code with
+ * the columns before it written and counted in *out_T (TSW_EHIP: nothing is copied back and *out_T = 0);
+ * the context stays usable. The goals of a run stay
+ * inside starts + pickups + deliveries (task goals come from there, swaps permute, rotations copy
+ * tick-start values): their tables are built once, before the first step (TSW_ENOMEM if the set does not
+ * fit table_budget_bytes). */
+int tsw_fleet_mapd(tsw_ctx *ctx, const tsw_point *starts, uint32_t n, const tsw_task *tasks, uint32_t m,
+                   uint32_t radius, uint32_t max_t, tsw_rec *out, uint32_t *goal_out, uint32_t *task_out,
+                   uint32_t *out_T, uint32_t *stalled);
 
 /* K1: BFS distance tables for k goal cells, u16 per cell, row-major
  * (TSW_DIST_INF for blocked/unreachable). out: host buffer k*w*h. */

@@ -125,6 +125,7 @@ EXPORTED_SYMBOLS = (
     "tsw_clear_tables", "tsw_get_stats", "tsw_reset_stats", "tsw_set_timing", "tsw_probe_round_floors",
     "tsw_abi_version", "tsw_plan_mapd_resolved", "tsw_next_hop_codes", "tsw_build_id",
     "tsw_host_next_hop_codes", "tsw_nearby", "tsw_decide_fleet", "tsw_fleet_apply", "tsw_fleet_run",
+    "tsw_fleet_mapd",
 )
 
 # tsw_resolve_fn (include/tswap.h): int (*)(void *user, uint32_t k, const uint32_t *start,
@@ -175,6 +176,8 @@ def load_library(path: str = LIB_PATH):
     lib.tsw_fleet_apply.restype = ctypes.c_int
     lib.tsw_fleet_run.argtypes = [vp, P(u32), P(u32), u32, u32, u32, P(u32), P(u32), P(u32)]
     lib.tsw_fleet_run.restype = ctypes.c_int
+    lib.tsw_fleet_mapd.argtypes = [vp, P(_Point), u32, P(_Task), u32, u32, u32, P(_Rec), P(u32), P(u32), P(u32), P(u32)]
+    lib.tsw_fleet_mapd.restype = ctypes.c_int
     lib.tsw_dist_tables.argtypes = [vp, P(u32), u32, P(ctypes.c_uint16)]
     lib.tsw_dist_tables_device.argtypes = [vp, P(u32), u32, vp]
     lib.tsw_import_tables_device.argtypes = [vp, P(u32), u32, vp]
@@ -499,6 +502,33 @@ class Planner:
         if record:
             return v, g, done.value, vr[:, :done.value + 1].copy(), gr[:, :done.value + 1].copy()
         return v, g, done.value
+
+    def fleet_mapd(self, starts_xy, tasks_xyxy, max_t: int = 2000, radius: int = 15, trace: bool = False):
+        """A MAPD run on the lock-step decentralized tick, resident on the device (tsw_fleet_mapd): an agent
+        without a task takes the next one of the stream, pickup and delivery are keyed on v == g, every
+        step is one tick. starts_xy: (n,2) uint32; tasks_xyxy: (m,4) uint32 (pickup x,y, delivery x,y).
+        Returns (rec, stalled), with trace=True (rec, goals, tasks, stalled): rec (n, T) uint64 packed
+        x | y<<16 | state<<32 exactly as plan_mapd_arrays packs it, goals / tasks (n, T) uint32 the goal cell
+        and the task index (0xFFFFFFFF: none) of every agent after each step, stalled True when the run
+        ended at a fixed point with tasks still open."""
+        starts = np.ascontiguousarray(starts_xy, dtype=np.uint32).reshape(-1, 2)
+        tasks = np.ascontiguousarray(tasks_xyxy, dtype=np.uint32).reshape(-1, 4)
+        n, m = starts.shape[0], tasks.shape[0]
+        max_t = int(max_t)
+        stride = max_t + 1 if 0 <= max_t <= 1 << 20 else 1  # past the limit the call fails before it writes
+        out = np.zeros((max(n, 1), stride), dtype=np.uint64)
+        goals = np.zeros((max(n, 1), stride), dtype=np.uint32) if trace else None
+        tks = np.zeros((max(n, 1), stride), dtype=np.uint32) if trace else None
+        T, stalled = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(self._lib.tsw_fleet_mapd(
+            self._ctx, starts.ctypes.data_as(ctypes.POINTER(_Point)), n, tasks.ctypes.data_as(ctypes.POINTER(_Task)),
+            m, radius, max_t, out.ctypes.data_as(ctypes.POINTER(_Rec)), _u32p(goals) if trace else None,
+            _u32p(tks) if trace else None, ctypes.byref(T), ctypes.byref(stalled)))
+        t = T.value
+        rec = out[:n, :t] & np.uint64(0xFFFFFFFFFF)
+        if trace:
+            return rec, goals[:n, :t].copy(), tks[:n, :t].copy(), bool(stalled.value)
+        return rec, bool(stalled.value)
 
     # --- get_path -----------------------------------------------------------
     def get_path_next(self, start: np.ndarray, goal: np.ndarray):

@@ -27,6 +27,7 @@
 #include "tsw_internal.h"
 #include "tsw_launch.h"
 #include "tsw_fleet.h"
+#include "tsw_fleet_mapd.h"
 #include "tsw_nearby.h"
 #include "tsw_plan.h"
 #include "tswap.h"
@@ -353,7 +354,7 @@ struct tsw_ctx {
   size_t tmp_cap = 0;
   // tsw_nearby / tsw_decide_fleet scratch (grow-only): [0] bins, counts and offsets (sized by the fleet
   // and the grid), [1] the lists and k_decide's arrays (sized by the lists' total)
-  // [2] tsw_fleet_run's records (v_rec | g_rec)
+  // [2] tsw_fleet_run's records (v_rec | g_rec) or tsw_fleet_mapd's (out | goal_out | task_out)
   uint32_t* d_fleet[3] = {nullptr, nullptr, nullptr};
   size_t fleet_cap[3] = {0, 0, 0};
   uint32_t* h_fleet = nullptr;  // pinned staging of tsw_decide_fleet: v | g up, act | cell | partner | part_off down
@@ -3018,6 +3019,198 @@ int tsw_fleet_run(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n, uint32_t rad
   TRY(set_device(c));
   // a failed round may leave queued pairs PENDING: reset them before returning the error
   return reset_pending_after(c, fleet_run_impl(c, v, g, n, radius, ticks, v_rec, g_rec, ticks_done));
+}
+
+// ---- K5c: a MAPD run on the lock-step tick (tsw_fleet_mapd.hip around the K5 / K5b pipeline) ----------
+
+// words of the MAPD state behind n agents and m tasks: st (n) and the counter words, cleared together;
+// tk (n); the idle flags (n + 1) and their scan's block sums; pick | dlv (2 m)
+static size_t fleet_mapd_words(uint32_t n, uint32_t m) {
+  return 3 * (size_t)n + MAPD_WORDS + 1 + nb_scan_blocks(n) + 2 * (size_t)m;
+}
+
+static int fleet_mapd_impl(tsw_ctx* c, const std::vector<uint32_t>& vcell, const std::vector<uint32_t>& pick,
+                           const std::vector<uint32_t>& dlv, uint32_t radius, uint32_t max_t, tsw_rec* out,
+                           uint32_t* goal_out, uint32_t* task_out, uint32_t* out_T, uint32_t* stalled) {
+  const uint32_t n = (uint32_t)vcell.size(), m = (uint32_t)pick.size();
+  // one ensure_tables for the whole run: task goals come from pick / dlv, swaps permute the goals and
+  // rotations copy tick-start goals, so every goal of the run is a start, a pickup or a delivery
+  {
+    std::vector<uint32_t> goals;
+    goals.reserve(n + 2 * (size_t)m);
+    goals.insert(goals.end(), vcell.begin(), vcell.end());
+    goals.insert(goals.end(), pick.begin(), pick.end());
+    goals.insert(goals.end(), dlv.begin(), dlv.end());
+    TRY(ensure_tables(c, goals, true));
+  }
+  FleetLists S;
+  uint32_t* extra = nullptr;
+  TRY(fleet_lists_setup(c, n, radius, &S, fleet_apply_words(n) + fleet_mapd_words(n, m), &extra));
+  TRY(fleet_hgrow(c, 2 * (size_t)n + 2 * (size_t)m + 4));
+  FleetApplyArgs A{};
+  fleet_apply_layout(&A, extra, n);
+  A.v = S.v;
+  A.g = S.g;
+  FleetMapdArgs M{};
+  M.n = n;
+  M.m = m;
+  M.W = c->G.W;
+  M.v = S.v;
+  M.g = S.g;
+  M.st = extra + fleet_apply_words(n);
+  M.words = M.st + n;
+  M.tk = M.words + MAPD_WORDS;
+  M.flag = M.tk + n;
+  M.bsum = M.flag + n + 1;
+  uint32_t* d_pick = M.bsum + nb_scan_blocks(n);
+  M.pick = d_pick;
+  M.dlv = d_pick + m;
+  M.tick_changed = A.changed;
+  // the records: tsw_rec (8 bytes) first, so that its columns are 8-byte aligned
+  const size_t stride = (size_t)max_t + 1, cols_words = (size_t)n * stride;
+  TRY(fleet_grow(c, 2, (2 + (goal_out ? 1 : 0) + (task_out ? 1 : 0)) * cols_words));
+  M.rec = reinterpret_cast<unsigned long long*>(c->d_fleet[2]);
+  M.g_rec = goal_out ? c->d_fleet[2] + 2 * cols_words : nullptr;
+  M.t_rec = task_out ? c->d_fleet[2] + (goal_out ? 3 : 2) * cols_words : nullptr;
+  M.rec_stride = max_t + 1;
+  // v | g (= v: an idle agent's goal is its own cell), and pick | dlv, through the staging buffer
+  uint32_t* h = c->h_fleet;
+  std::memcpy(h, vcell.data(), n * 4ull);
+  std::memcpy(h + n, vcell.data(), n * 4ull);
+  HIPCHK(hipMemcpyAsync(S.v, h, 2ull * n * 4, hipMemcpyHostToDevice, c->s));
+  if (m) {
+    std::memcpy(h + 2 * (size_t)n, pick.data(), m * 4ull);
+    std::memcpy(h + 2 * (size_t)n + m, dlv.data(), m * 4ull);
+    HIPCHK(hipMemcpyAsync(d_pick, h + 2 * (size_t)n, 2ull * m * 4, hipMemcpyHostToDevice, c->s));
+  }
+  HIPCHK(hipMemsetAsync(M.st, 0, ((size_t)n + MAPD_WORDS) * 4, c->s));  // IDLE, next = 0, no stamp yet
+  HIPCHK(hipMemsetAsync(M.tk, 0xFF, n * 4ull, c->s));                   // MAPD_NO_TASK
+  HIPCHK(hipMemsetAsync(A.changed, 0, 4, c->s));
+  // Step s writes column s (every step before it was recorded, or the run had ended). Its three facts
+  // reach the host as one status word inside step s + 1's count-pass read-back, so a step synchronises
+  // exactly as often as a tsw_fleet_run tick does. The count pass reads positions only, which stage 1
+  // does not touch: it runs ahead of stage 1, and when the status ends the run nothing of step s + 1
+  // has changed the state. Behind step max_t there is no count pass: the word comes in a copy of its own.
+  constexpr uint32_t NOT_READ = 0xFFFFFFFFu;
+  uint32_t cols = 0;
+  bool stall = false;
+  int rc = TSW_OK;
+  for (uint32_t s = 0;; ++s) {
+    uint32_t status = NOT_READ;
+    if (s <= max_t) {
+      rc = fleet_lists_count(c, &S, M.words + MAPD_STATUS, &status);
+    } else {
+      if (hipMemcpyAsync(h, M.words + MAPD_STATUS, 4, hipMemcpyDeviceToHost, c->s) == hipSuccess &&
+          hipStreamSynchronize(c->s) == hipSuccess) {
+        status = h[0];
+      } else {
+        c->err = "reading the last step's status failed";
+        rc = TSW_EHIP;
+      }
+    }
+    // The ending decision of step s - 1. When the read-back itself failed (a HIP error: status stays
+    // NOT_READ) step s - 1 cannot be judged and is not counted, although its column exists on the device;
+    // TSW_EHIP copies nothing back anyway. Every other failure of step s arrives with the status read.
+    if (s > 0 && status != NOT_READ) {
+      if (status & MAPD_S_STUCK) {
+        c->err = "internal: the goal-op rounds made no progress";
+        rc = TSW_EHIP;
+        break;
+      }
+      if (status & MAPD_S_DONE) {
+        cols = s;
+        rc = TSW_OK;
+        break;
+      }
+      if (!(status & (MAPD_S_TASK | MAPD_S_TICK))) {  // a fixed point: step s - 1 is not recorded
+        stall = true;
+        rc = TSW_OK;
+        break;
+      }
+      cols = s;
+    }
+    if (rc != TSW_OK || s > max_t) break;  // a failing step, or the horizon (tswap.rs:167)
+    M.stamp = A.stamp = s + 1;
+    M.rec_col = s;
+    hipError_t e = launch_fleet_mapd_tasks(M, c->s);
+    if (e != hipSuccess) {
+      c->err = std::string("launch_fleet_mapd_tasks failed: ") + hipGetErrorString(e);
+      rc = TSW_EHIP;
+      break;
+    }
+    DecideDev D{};
+    uint32_t *d_poff, *d_pout;
+    if ((rc = fleet_decide_device(c, S, 0xFFFFFFFFu, &D, &d_poff, &d_pout)) != TSW_OK) break;
+    A.act = D.act;
+    A.cell = D.cell;
+    A.partner = D.par;
+    A.part_off = d_poff;
+    A.part = d_pout;
+    e = launch_fleet_apply(A, c->s);
+    if (e == hipSuccess) e = launch_fleet_mapd_record(M, c->s);
+    if (e != hipSuccess) {
+      c->err = std::string("launch_fleet_apply / launch_fleet_mapd_record failed: ") + hipGetErrorString(e);
+      rc = TSW_EHIP;
+      break;
+    }
+  }
+  // the records come down once: columns 0 .. cols - 1 of every agent's row, the later ones stay as the
+  // caller left them
+  auto copy_back = [&]() -> int {
+    struct {
+      void* host;
+      const void* dev;
+      size_t elem;
+    } recs[3] = {{out, M.rec, 8}, {goal_out, M.g_rec, 4}, {task_out, M.t_rec, 4}};
+    for (const auto& r : recs) {
+      if (!r.host) continue;
+      if (cols == stride)
+        HIPCHK(hipMemcpyAsync(r.host, r.dev, cols_words * r.elem, hipMemcpyDeviceToHost, c->s));
+      else
+        HIPCHK(hipMemcpy2DAsync(r.host, stride * r.elem, r.dev, stride * r.elem, (size_t)cols * r.elem, n,
+                                hipMemcpyDeviceToHost, c->s));
+    }
+    HIPCHK(hipStreamSynchronize(c->s));
+    return TSW_OK;
+  };
+  if (rc == TSW_OK) {
+    if (cols) rc = copy_back();
+    if (rc == TSW_OK) {  // a copy back that fails delivered no complete column: *out_T stays 0
+      *out_T = cols;
+      if (stalled) *stalled = stall ? 1u : 0u;
+    }
+  } else if (rc != TSW_EHIP && cols > 0) {  // a failing step keeps its code, whatever the copy back does
+    const std::string msg = c->err;
+    if (copy_back() == TSW_OK) *out_T = cols;
+    c->err = msg;
+  }
+  resolve_timing(c);
+  return rc;
+}
+
+int tsw_fleet_mapd(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_task* tasks, uint32_t m, uint32_t radius,
+                   uint32_t max_t, tsw_rec* out, uint32_t* goal_out, uint32_t* task_out, uint32_t* out_T,
+                   uint32_t* stalled) {
+  if (!c) return TSW_EINVAL;
+  NOT_FROM_RESOLVER(c);
+  if (!out_T || (n && (!starts || !out)) || (m && !tasks)) RET(TSW_EINVAL, "null argument");
+  *out_T = 0;
+  if (stalled) *stalled = 0;
+  if (max_t > (1u << 20)) RET(TSW_EINVAL, "max_t too large");
+  // every cell a kernel would index with, checked before anything is launched; all m tasks, dispatched
+  // or not (the model is this library's own: there is no reference panic site to imitate)
+  std::vector<uint32_t> vcell(n), pick(m), dlv(m);
+  for (uint32_t i = 0; i < n; ++i)
+    if (!cell_ok(c, starts[i].x, starts[i].y, &vcell[i])) RET(TSW_EINVAL, "start position off-grid or blocked");
+  for (uint32_t k = 0; k < m; ++k)
+    if (!cell_ok(c, tasks[k].pickup.x, tasks[k].pickup.y, &pick[k]) ||
+        !cell_ok(c, tasks[k].delivery.x, tasks[k].delivery.y, &dlv[k]))
+      RET(TSW_EINVAL, "task pickup or delivery off-grid or blocked");
+  if (n == 0) return TSW_OK;
+  TRY(set_device(c));
+  // a failed round may leave queued pairs PENDING: reset them before returning the error
+  return reset_pending_after(
+      c, fleet_mapd_impl(c, vcell, pick, dlv, radius, max_t, out, goal_out, task_out, out_T, stalled));
 }
 
 int tsw_get_path_next(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, uint32_t k, uint32_t* next,

@@ -169,6 +169,9 @@ extern "C" {
                            partner: *const u32, part_off: *const u32, part: *const u32) -> c_int;
     pub fn tsw_fleet_run(ctx: *mut TswCtx, v: *mut u32, g: *mut u32, n: u32, radius: u32, ticks: u32,
                          v_rec: *mut u32, g_rec: *mut u32, ticks_done: *mut u32) -> c_int;
+    pub fn tsw_fleet_mapd(ctx: *mut TswCtx, starts: *const TswPoint, n: u32, tasks: *const TswTask, m: u32,
+                          radius: u32, max_t: u32, out: *mut TswRec, goal_out: *mut u32, task_out: *mut u32,
+                          out_t: *mut u32, stalled: *mut u32) -> c_int;
     pub fn tsw_dist_tables(ctx: *mut TswCtx, goals: *const u32, k: u32, out: *mut u16) -> c_int;
     pub fn tsw_dist_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_out: *mut u16) -> c_int;
     pub fn tsw_import_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_tables: *const u16) -> c_int;
