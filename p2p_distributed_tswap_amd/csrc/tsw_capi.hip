@@ -99,7 +99,7 @@ struct Tunables {
   int worker_fb = -1;             // TSW_WORKER_FB=0 / 1: global-g-score workers without / with the staged free bitmap (-1: by waves per CU)
   bool dag_exit = true;           // TSW_DAG_EXIT=0: coop workers' A* runs to the goal's pop (no DAG early exit)
   uint32_t dag_mask = 0;          // TSW_DAG_MASK: the DAG early-exit test runs every (mask + 1) pops (0: auto)
-  uint32_t ab_flags = 0;          // TSW_AB_FLAGS (A/B): 1 no 2-cycle fast path, 2 no end-of-rules prefetch, 4 one agent per K4 batch, 8 no batched rules walks
+  uint32_t ab_flags = 0;          // TSW_AB_FLAGS (A/B): 1 no 2-cycle fast path, 2 no end-of-rules prefetch, 4 one agent per K4 batch, 8 no batched rules walks, 16 K4 batches of at most 8, 32 K4 scan list of 4 entries
   uint32_t t0_delay_us = 0;       // TSW_T0_DELAY_US (A/B): the planner idles this long after step 0's assignment
   uint32_t stale_steps = 16;      // TSW_SPEC_STALE: coop workers drop speculative pairs older than this many steps (0: never)
   uint32_t reg_heap = 63;         // TSW_ASTAR_REGHEAP: worker A* heaps up to this many entries in registers (0: LDS only)
@@ -1830,10 +1830,15 @@ int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
       c->st.rule_rounds += k.rule_rounds;
       c->st.move_rounds += k.move_rounds;
       if (c->tun.plan_debug) {
-        unsigned long long tk[48];
+        unsigned long long tk[64];
         HIPCHK(hipMemcpy(tk, c->d_ticks, sizeof tk, hipMemcpyDeviceToHost));
         fprintf(stderr, "[k_plan] assign us: transitions %.0f compaction %.0f scan %.0f accept %.0f update %.0f | sections %llu batches %llu accepted %llu\n",
                 tk[32] / 100.0, tk[33] / 100.0, tk[34] / 100.0, tk[35] / 100.0, tk[36] / 100.0, tk[39], tk[37], tk[38]);
+        // the scan's parts as thread 0 sees them (the closing part includes its wait for the slowest wave)
+        fprintf(stderr, "[k_plan] assign scan us: index %.0f bound %.0f entries %.0f reduce %.0f | chunk-agent pairs %llu chunks %llu "
+                "scanning waves %llu list rounds %llu | batch widths 1: %llu 2-4: %llu 5-8: %llu 9-16: %llu\n",
+                tk[48] / 100.0, tk[49] / 100.0, tk[50] / 100.0, tk[51] / 100.0, tk[52], tk[53], tk[54], tk[60], tk[55], tk[56],
+                tk[57], tk[58]);
         fprintf(stderr, "[k_plan] PRE1 publish us %.0f (%llu) | rules init us %.0f prefetch us %.0f publish us %.0f (%llu)\n",
                 tk[24] / 100.0, tk[25], tk[26] / 100.0, tk[27] / 100.0, tk[28] / 100.0, tk[29]);
         fprintf(stderr, "[k_plan] wave rules kcycles: load %.0f stale %.0f fast %.0f update %.0f slow %.0f rot %.0f | "
@@ -2256,8 +2261,8 @@ tsw_ctx* tsw_create(const uint8_t* cells, uint32_t w, uint32_t h, const tsw_opts
     return fail("pinned status", e);
   if ((e = hipMalloc(&c->d_ctl, sizeof(PlanCtl))) != hipSuccess) return fail("malloc ctl", e);
   if ((e = hipMalloc(&c->d_pargs, sizeof(PlanArgs))) != hipSuccess) return fail("malloc plan args", e);
-  if ((e = hipMalloc(&c->d_ticks, 48 * sizeof(unsigned long long))) != hipSuccess) return fail("malloc ticks", e);
-  if ((e = hipMemsetAsync(c->d_ticks, 0, 48 * sizeof(unsigned long long), c->s)) != hipSuccess)
+  if ((e = hipMalloc(&c->d_ticks, 64 * sizeof(unsigned long long))) != hipSuccess) return fail("malloc ticks", e);
+  if ((e = hipMemsetAsync(c->d_ticks, 0, 64 * sizeof(unsigned long long), c->s)) != hipSuccess)
     return fail("memset ticks", e);
   hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, c->device);
   if (c->wall_khz <= 0) c->wall_khz = 100000;
@@ -3487,7 +3492,7 @@ int tsw_reset_stats(tsw_ctx* c) {
   const uint64_t tabs = c->st.tables;
   c->st = tsw_stats{};
   c->st.tables = tabs;
-  if (c->d_ticks) (void)hipMemsetAsync(c->d_ticks, 0, 48 * sizeof(unsigned long long), c->s);
+  if (c->d_ticks) (void)hipMemsetAsync(c->d_ticks, 0, 64 * sizeof(unsigned long long), c->s);
   return TSW_OK;
 }
 

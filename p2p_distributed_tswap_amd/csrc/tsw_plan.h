@@ -151,7 +151,8 @@ struct PlanArgs {
   uint64_t* rec;
   uint32_t* grec;
   PlanCtl* ctl;
-  unsigned long long* sec_ticks;  // [48] wall-clock ticks per section [0..7], sub-phase ticks and counters [8..47] (diagnostics)
+  unsigned long long* sec_ticks;  // [64] wall-clock ticks per section [0..7], sub-phase ticks and counters [8..47] (diagnostics);
+                                  // [48..63]: K4 scan parts and counters, added to in place (diagnostics)
   uint32_t dbg;                   // sub-phase ticks on (TSW_PLAN_DEBUG)
   uint32_t* dtag;                 // diagnostics (TSW_PLAN_DEBUG): per agent, what changed it since PRE1 (CoopCtl::dbg_tag)
   // coop mode: K3 runs concurrently in the dispatch's worker workgroups (tsw_worker.h); Q is the needed queue (qcap entries for the

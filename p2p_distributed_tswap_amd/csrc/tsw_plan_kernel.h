@@ -104,7 +104,9 @@ constexpr uint32_t OCC_IDX = 0x7FFFFFFFu;
 constexpr uint32_t SUCC_TERM = 0xFFFFFFFFu;
 constexpr uint32_t NO_AGENT = 0xFFFFFFFFu;
 constexpr uint32_t NO_CELL = 0xFFFFFFFFu;
-constexpr uint32_t ABATCH = 8;    // K4: idle agents whose nearest pickups one pass over the tasks computes
+constexpr uint32_t ABATCH = 16;   // K4: idle agents whose nearest pickups one pass over the tasks computes (a multiple of 4, <= 32)
+constexpr uint32_t SCAN_CAP = 64;  // K4: (chunk, agent mask) entries of the scan's LDS list when it lies in s_ap (two words each)
+constexpr uint32_t SCAN_GRP = 4;   // K4: list entries a half-wave loads before it compares them
 constexpr uint32_t KCH = 32;      // K4: tasks per spatial chunk (PlanArgs::kbox / kcnt), a multiple of 16
 constexpr uint32_t KPT = 2;       // K4: chunks per thread whose count and box stay in registers across a batch
 constexpr uint32_t LIST_CAP = 1024;  // entries of the kernel's LDS `list` (ASSIGN compaction, changed agents)
@@ -1044,6 +1046,51 @@ __device__ bool walk_move(const PlanArgs& P, const Arrays& S, PlanCtl& ctl) {
   return true;
 }
 
+// K4: the block reads the nl chunks of the scan's list (two words an entry: chunk, mask of the batch agents it
+// matters to) with one lane per index entry — half a wave per chunk, SCAN_GRP list entries per half-wave at a
+// time with their loads in flight together — and merges each agent's minimum of (distance, task index) into
+// bestk with one 64-bit LDS atomicMin per wave. Out of line, so that its registers are a call's clobber set
+// (below nextnext_prefetch's) and not part of the planner body's allocation.
+__device__ __noinline__ void scan_walk(const uint32_t* slist, uint32_t nl, const uint32_t* apos, uint64_t* bestk,
+                                       const uint32_t* live, const uint32_t* klt, unsigned long long* dbg_ticks) {
+  const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  for (uint32_t e0 = 0; e0 < nl; e0 += SCAN_GRP * 2u * nwaves) {  // block-uniform
+    uint32_t cm0[SCAN_GRP], xy[SCAN_GRP], tk[SCAN_GRP];
+#pragma unroll
+    for (uint32_t q = 0; q < SCAN_GRP; ++q) {
+      const uint32_t ei = e0 + q * 2u * nwaves + 2u * wid + (lane >> 5);
+      cm0[q] = 0u;
+      xy[q] = TASK_TAKEN;
+      tk[q] = 0xFFFFFFFFu;
+      if (ei < nl) {
+        const size_t ep = (size_t)slist[2u * ei] * KCH + (lane & 31u);
+        cm0[q] = slist[2u * ei + 1u];
+        xy[q] = live[ep];
+        tk[q] = klt[ep];
+      }
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < SCAN_GRP; ++q) {
+      uint32_t um = (uint32_t)__builtin_amdgcn_readlane((int)cm0[q], 0) |
+                    (uint32_t)__builtin_amdgcn_readlane((int)cm0[q], 32);
+      if (dbg_ticks && lane == 0 && um != 0u) atomicAdd(&dbg_ticks[54], 1ull);  // diagnostics: waves with an entry
+      const uint32_t cm = xy[q] == TASK_TAKEN ? 0u : cm0[q];
+      const uint32_t tx = xy[q] & 0xFFFFu, ty = xy[q] >> 16;
+      while (um != 0u) {  // wave-uniform: the agents either half's chunk matters to
+        const uint32_t b = (uint32_t)__builtin_ctz(um);
+        um &= um - 1u;
+        const uint32_t pa = apos[b];
+        const uint32_t d = ((cm >> b) & 1u) ? __usad(pa & 0xFFFFu, tx, __usad(pa >> 16, ty, 0u)) : 0xFFFFFFFFu;
+        const uint32_t dm = __ockl_wfred_min_u32(d);
+        if (dm == 0xFFFFFFFFu) continue;
+        const uint32_t tm = __ockl_wfred_min_u32(d == dm ? tk[q] : 0xFFFFFFFFu);
+        if (lane == 0)
+          atomicMin(reinterpret_cast<unsigned long long*>(&bestk[b]), ((unsigned long long)dm << 32) | tm);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // diagnostics: wall-clock ticks of sub-phases (P.sec_ticks[8..15], printed by TSW_PLAN_DEBUG)
@@ -1059,6 +1106,20 @@ __device__ bool walk_move(const PlanArgs& P, const Arrays& S, PlanCtl& ctl) {
       s_tick[slot] += nw_ - s_tp;                    \
       s_tp = nw_;                                    \
     }                                                \
+  } while (0)
+
+// diagnostics: the K4 scan's parts (thread 0's wall clock) and counters, added in place to P.sec_ticks[48..63]
+#define SCAN_TICK(slot)                                              \
+  do {                                                               \
+    if (PLAN_DBG && tid == 0 && P.sec_ticks) {                       \
+      const unsigned long long nw_ = wall_clock64();                 \
+      atomicAdd(&P.sec_ticks[slot], nw_ - s_tp2);                    \
+      s_tp2 = nw_;                                                   \
+    }                                                                \
+  } while (0)
+#define SCAN_COUNT(slot, v)                                                                   \
+  do {                                                                                        \
+    if (PLAN_DBG && P.sec_ticks) atomicAdd(&P.sec_ticks[slot], (unsigned long long)(v));      \
   } while (0)
 
 // AG: every agent array in LDS. OC: the occupancy grid OCC in LDS; MUL: the movement rounds' MU
@@ -1096,12 +1157,13 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
   __shared__ PlanCtl s_ctl;
   __shared__ uint32_t s_q[12], s_need, s_cnt, s_doit, s_px, s_py, s_exit, s_best, s_miss, s_flag, s_abort, s_cabort, s_hops,
       s_badat;
-  __shared__ uint32_t s_ap[128];  // rules: members of a rule-4 cycle rotated by the wave (<= 64), links
+  __shared__ uint32_t s_ap[128];  // rules: members of a rule-4 cycle rotated by the wave (<= 64), links; K4: the scan's chunk list
   __shared__ uint32_t s_wcount[16];
   __shared__ uint64_t s_red[16];
   __shared__ uint64_t s_bestk[ABATCH];  // K4: per batch agent, block minimum of (distance, task) (LDS atomic min)
   __shared__ uint32_t s_apos[ABATCH], s_acct[ABATCH], s_cnt2, s_ub[ABATCH];
-  __shared__ unsigned long long s_tick[48], s_tlast, s_tp;
+  __shared__ uint32_t s_lcnt, s_more;  // K4: entries appended to the scan's list this round / chunks left for another round
+  __shared__ unsigned long long s_tick[48], s_tlast, s_tp, s_tp2;
   __shared__ uint32_t s_tsec;
   __shared__ uint32_t s_bad;               // ASSIGN looked up an off-grid/blocked task cell
   __shared__ uint32_t s_nassign, s_npick;  // diagnostics: this step's assignments / pickup arrivals
@@ -1292,7 +1354,7 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
       // parallel. The assignments depend on each other (a task taken by an earlier agent is gone): the
       // idle agents are taken in index order in adaptive batches of up to ABATCH. One block-wide pass
       // computes every batch agent's first minimum of (Manhattan distance, task index) over the Morton
-      // index, reading only chunks whose box lower bound is within the agent's current bound; thread 0
+      // index, reading only chunks whose box lower bound is within the agent's current bound; wave 0
       // then accepts the minima in agent order up to the first agent whose task an earlier batch agent
       // took (it and the rest re-run in the next batch). An accepted minimum was taken over a superset of
       // the tasks unused at its sequential turn and is still unused, so it is min_by_key's lowest-index
@@ -1359,151 +1421,186 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
         PLAN_TICK(33);
         const uint32_t cnt = s_cnt, bad_at = s_badat;
         // Assignments in batches of up to ABATCH agents (index order): one block-wide pass computes every
-        // batch agent's first minimum over the unused tasks at once, then thread 0 accepts them in agent
+        // batch agent's first minimum over the unused tasks at once, then wave 0 accepts them in agent
         // order up to the first agent whose task an earlier agent of the batch took (that agent and the
         // rest re-run in the next batch, against the updated LIVE array). An accepted agent's minimum was
         // taken over a superset of what was unused at its sequential turn and its task is still unused,
         // so it IS the sequential first minimum (min_by_key, tswap.rs:125-130).
         // batch size adapts: it doubles after a batch without a conflict and drops to the accepted count
         // after one (the t = 0 burst of a dense instance conflicts often; a busy step's handful rarely)
-        uint32_t bcur = (kab & 4u) ? 1u : ABATCH;
+        const uint32_t wmax = (kab & 4u) ? 1u : (kab & 16u) ? 8u : ABATCH;  // (A/B, diagnostic build: 4, 16)
+        uint32_t bcur = wmax;
+        // The scan's chunk list: what `list` leaves free behind the step's idle agents (C3: ~12 of its 1,024 words
+        // in a busy step, so ~500 entries), else the SCAN_CAP entries of s_ap (a t = 0 burst fills `list`).
+        // (A/B 32: 4 entries, so that small instances take several rounds over the list too.)
+        const bool ltail = !(kab & 32u) && (LIST_CAP - cnt) / 2u > SCAN_CAP;  // block-uniform
+        uint32_t* const slist = ltail ? list + cnt : s_ap;
+        const uint32_t lcap = (kab & 32u) ? 4u : ltail ? (LIST_CAP - cnt) / 2u : SCAN_CAP;
+        auto box_lb = [](uint32_t pa, uint32_t lo, uint32_t hi) -> uint32_t {  // distance from pa to a box
+          const uint32_t px = pa & 0xFFFFu, py = pa >> 16;
+          const uint32_t x0 = lo & 0xFFFFu, y0 = lo >> 16, x1 = hi & 0xFFFFu, y1 = hi >> 16;
+          const uint32_t dx = px < x0 ? x0 - px : (px > x1 ? px - x1 : 0u);
+          const uint32_t dy = py < y0 ? y0 - py : (py > y1 ? py - y1 : 0u);
+          return dx + dy;
+        };
+        // Index words. A thread's first KPT chunks (every chunk while kchunks <= KPT * block) stay in
+        // registers for the whole step: the boxes are static, and the counts change only through this
+        // block's own atomicSub in a batch's update, after whose barrier they are read again (the load is
+        // in flight while the next batch is set up). Any further chunks are re-read where they are used.
+        const uint32_t nch = P.kchunks;
+        uint32_t kc[KPT];
+        uint2 kb[KPT];
+#pragma unroll
+        for (uint32_t s = 0; s < KPT; ++s) {
+          const uint32_t c = tid + s * bd;
+          kc[s] = (cnt != 0u && c < nch) ? P.kcnt[c] : 0u;
+          kb[s] = (cnt != 0u && c < nch) ? P.kbox[c] : make_uint2(0u, 0u);
+        }
         for (uint32_t kk = 0; kk < cnt && !s_bad;) {
           const uint32_t B = min(bcur, cnt - kk);
-          if (tid < B) {
-            const uint32_t v = S.V[list[kk + tid]];
-            s_apos[tid] = (v % W) | ((v / W) << 16);
+          if (tid < ABATCH) {
+            uint32_t ap = 0u;
+            if (tid < B) {
+              const uint32_t v = S.V[list[kk + tid]];
+              ap = (v % W) | ((v / W) << 16);
+            }
+            s_apos[tid] = ap;
             s_bestk[tid] = ~0ull;
             s_ub[tid] = 0xFFFFFFFFu;
           }
+          if (tid == 0) s_lcnt = s_more = 0u;
           PBAR();
+          if (PLAN_DBG && tid == 0) {
+            s_tp2 = wall_clock64();
+            SCAN_COUNT(B == 1u ? 55 : B <= 4u ? 56 : B <= 8u ? 57 : 58, 1);
+          }
           // Spatially pruned scan. The host orders the tasks along a Morton curve of their pickup points and
           // cuts that order into chunks of KCH entries with a bounding box each (static) and a count of
           // untaken entries (KCNT). Phase A: a chunk with an untaken entry holds one within
           // lb + diam of an agent (lb: distance to its box), so U_b = min over such chunks of lb + diam
           // bounds agent b's minimum from above. Phase B: only chunks with lb <= U_b can hold a task at
-          // the minimum distance (ties included); their entries are compared as (distance, task index).
-          uint32_t apos[ABATCH], ub[ABATCH];
+          // the minimum distance (ties included). The threads that own such a chunk append (chunk, mask
+          // of the batch agents it matters to) to a list in LDS, and the block then reads the listed
+          // chunks with one lane per entry: half a wave per chunk, LIVE and KLT loaded coalesced, each
+          // lane's entry compared as (distance, task index) for the agents of its chunk's mask, a wave
+          // minimum per agent and one 64-bit LDS atomicMin per wave and agent. The key alone orders the
+          // result, so neither the list order nor the arrival order of the atomics matters.
+          // Phase A, four batch agents at a time (entries of s_apos past B are zero and never stored)
+          for (uint32_t b0 = 0; b0 < B; b0 += 4u) {  // block-uniform
+            uint32_t u[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+            const uint32_t pa[4] = {s_apos[b0], s_apos[b0 + 1u], s_apos[b0 + 2u], s_apos[b0 + 3u]};
+            auto ub_chunk = [&](uint32_t ccnt, uint2 bx) {
+              if (ccnt == 0u) return;
+              const uint32_t diam = ((bx.y & 0xFFFFu) - (bx.x & 0xFFFFu)) + ((bx.y >> 16) - (bx.x >> 16));
 #pragma unroll
-          for (uint32_t b = 0; b < ABATCH; ++b) {
-            apos[b] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(b < B ? s_apos[b] : 0u));
-            ub[b] = 0xFFFFFFFFu;
-          }
-          auto box_lb = [](uint32_t pa, uint32_t lo, uint32_t hi) -> uint32_t {  // distance from pa to a box
-            const uint32_t px = pa & 0xFFFFu, py = pa >> 16;
-            const uint32_t x0 = lo & 0xFFFFu, y0 = lo >> 16, x1 = hi & 0xFFFFu, y1 = hi >> 16;
-            const uint32_t dx = px < x0 ? x0 - px : (px > x1 ? px - x1 : 0u);
-            const uint32_t dy = py < y0 ? y0 - py : (py > y1 ? py - y1 : 0u);
-            return dx + dy;
-          };
-          // a thread's first KPT chunks (every chunk while kchunks <= KPT * block) are loaded once, all
-          // loads in flight together, and kept in registers for phase B; any further chunks are re-read
-          const uint32_t nch = P.kchunks;
-          uint32_t kc[KPT];
-          uint2 kb[KPT];
+              for (uint32_t j = 0; j < 4u; ++j) u[j] = min(u[j], box_lb(pa[j], bx.x, bx.y) + diam);
+            };
 #pragma unroll
-          for (uint32_t s = 0; s < KPT; ++s) {
-            const uint32_t c = tid + s * bd;
-            kc[s] = c < nch ? P.kcnt[c] : 0u;
-            kb[s] = c < nch ? P.kbox[c] : make_uint2(0u, 0u);
-          }
-          auto ub_chunk = [&](uint32_t cnt, uint2 bx) {
-            if (cnt == 0u) return;
-            const uint32_t diam = ((bx.y & 0xFFFFu) - (bx.x & 0xFFFFu)) + ((bx.y >> 16) - (bx.x >> 16));
+            for (uint32_t s = 0; s < KPT; ++s) ub_chunk(kc[s], kb[s]);
+            for (uint32_t c = tid + KPT * bd; c < nch; c += bd) ub_chunk(P.kcnt[c], P.kbox[c]);
 #pragma unroll
-            for (uint32_t b = 0; b < ABATCH; ++b) {
-              if (b >= B) break;  // block-uniform
-              ub[b] = min(ub[b], box_lb(apos[b], bx.x, bx.y) + diam);
+            for (uint32_t j = 0; j < 4u; ++j) {
+              const uint32_t wm = __ockl_wfred_min_u32(u[j]);
+              if (lane == 0 && b0 + j < B) atomicMin(&s_ub[b0 + j], wm);
             }
-          };
-#pragma unroll
-          for (uint32_t s = 0; s < KPT; ++s) ub_chunk(kc[s], kb[s]);
-          for (uint32_t c = tid + KPT * bd; c < nch; c += bd) ub_chunk(P.kcnt[c], P.kbox[c]);
-#pragma unroll
-          for (uint32_t b = 0; b < ABATCH; ++b) {
-            if (b >= B) break;
-            const uint32_t wm = __ockl_wfred_min_u32(ub[b]);
-            if (lane == 0) atomicMin(&s_ub[b], wm);
           }
           PBAR();
-          uint32_t bdst[ABATCH], btsk[ABATCH];
+          SCAN_TICK(49);
+          // Phase B. (sl, sc): this thread's next chunk to offer, sm: the batch agents it matters to
+          uint32_t sl = 0, sc = tid, sm = 0;
+          auto seek = [&]() {  // the thread's next chunk, from (sl, sc) on, within some batch agent's bound
+            for (sm = 0u; sc < nch; ++sl, sc += bd) {
+              uint32_t ccnt = 0;
+              uint2 bx = make_uint2(0u, 0u);
+              if (sl < KPT) {
 #pragma unroll
-          for (uint32_t b = 0; b < ABATCH; ++b) {
-            ub[b] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(b < B ? s_ub[b] : 0u));
-            bdst[b] = 0xFFFFFFFFu;
-            btsk[b] = 0xFFFFFFFFu;
-          }
-          auto scan_chunk = [&](uint32_t c, uint32_t cnt, uint2 bx) {
-            if (cnt == 0u) return;
-            uint32_t mask = 0;
-#pragma unroll
-            for (uint32_t b = 0; b < ABATCH; ++b)
-              if (b < B && box_lb(apos[b], bx.x, bx.y) <= ub[b]) mask |= 1u << b;
-            if (mask == 0u) return;
-            const uint4* L4 = reinterpret_cast<const uint4*>(P.live + (size_t)c * KCH);
-            const uint4* T4 = reinterpret_cast<const uint4*>(P.klt + (size_t)c * KCH);
-#pragma unroll 1
-            for (uint32_t h = 0; h < KCH / 16u; ++h) {  // 16 entries (4 vectors of each array) at a time
-              uint4 xa[4], ta[4];
-#pragma unroll
-              for (uint32_t u = 0; u < 4u; ++u) {
-                xa[u] = L4[4u * h + u];
-                ta[u] = T4[4u * h + u];
-              }
-#pragma unroll
-              for (uint32_t u = 0; u < 4u; ++u) {
-                const uint32_t xs[4] = {xa[u].x, xa[u].y, xa[u].z, xa[u].w};
-                const uint32_t ts[4] = {ta[u].x, ta[u].y, ta[u].z, ta[u].w};
-#pragma unroll
-                for (uint32_t e = 0; e < 4u; ++e) {
-                  const uint32_t xy = xs[e], t = ts[e];
-                  if (xy == TASK_TAKEN) continue;
-                  const uint32_t tx = xy & 0xFFFFu, ty = xy >> 16;
-#pragma unroll
-                  for (uint32_t b = 0; b < ABATCH; ++b) {
-                    if (b >= B) break;  // block-uniform
-                    if (!((mask >> b) & 1u)) continue;
-                    const uint32_t d = __usad(apos[b] & 0xFFFFu, tx, __usad(apos[b] >> 16, ty, 0u));
-                    const bool lt = d < bdst[b] || (d == bdst[b] && t < btsk[b]);
-                    bdst[b] = lt ? d : bdst[b];
-                    btsk[b] = lt ? t : btsk[b];
+                for (uint32_t s = 0; s < KPT; ++s)
+                  if (s == sl) {
+                    ccnt = kc[s];
+                    bx = kb[s];
                   }
+              } else {
+                ccnt = P.kcnt[sc];
+                if (ccnt != 0u) bx = P.kbox[sc];
+              }
+              if (ccnt == 0u) continue;
+              for (uint32_t b0 = 0; b0 < B; b0 += 4u) {
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; ++j)
+                  if (box_lb(s_apos[b0 + j], bx.x, bx.y) <= s_ub[b0 + j]) sm |= 1u << (b0 + j);
+              }
+              sm &= B >= 32u ? 0xFFFFFFFFu : (1u << B) - 1u;
+              if (sm != 0u) {
+                if (PLAN_DBG) {
+                  SCAN_COUNT(52, __popc(sm));
+                  SCAN_COUNT(53, 1);
                 }
+                return;
               }
             }
           };
-#pragma unroll
-          for (uint32_t s = 0; s < KPT; ++s) scan_chunk(tid + s * bd, kc[s], kb[s]);
-          for (uint32_t c = tid + KPT * bd; c < nch; c += bd) scan_chunk(c, P.kcnt[c], P.kbox[c]);
-#pragma unroll
-          for (uint32_t b = 0; b < ABATCH; ++b) {
-            if (b >= B) break;  // block-uniform
-            const uint32_t dm = __ockl_wfred_min_u32(bdst[b]);
-            const uint32_t tm = __ockl_wfred_min_u32(bdst[b] == dm ? btsk[b] : 0xFFFFFFFFu);
-            if (lane == 0 && dm != 0xFFFFFFFFu)
-              atomicMin(reinterpret_cast<unsigned long long*>(&s_bestk[b]), ((unsigned long long)dm << 32) | tm);
-          }
-          PBAR();
-          PLAN_TICK(34);
-          if (tid == 0) {
-            uint32_t acc = 0, stop = 0;
-            for (uint32_t b = 0; b < B; ++b) {
-              if (list[kk + b] > bad_at || s_ctl.unused == 0u || s_bestk[b] == ~0ull) {
-                stop = 1;  // past the first bad delivery / out of tasks: this step assigns no more
+          seek();
+          for (;;) {
+            // append: a wave reserves a run of list entries for its lanes that hold a chunk; what does
+            // not fit stays with its thread for the next round over the list (s_more)
+            for (;;) {  // wave-uniform
+              const uint64_t hb = __ballot(sm != 0u);
+              if (hb == 0ull) break;
+              uint32_t lb0 = 0;
+              if (lane == 0) lb0 = atomicAdd(&s_lcnt, (uint32_t)__popcll(hb));
+              lb0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lb0);
+              if (lb0 >= lcap) {
+                if (lane == 0) s_more = 1u;
                 break;
               }
-              const uint32_t t = (uint32_t)(s_bestk[b] & 0xFFFFFFFFu);
-              bool taken = false;
-              for (uint32_t e = 0; e < acc; ++e) taken |= s_acct[e] == t;
-              if (taken) break;  // conflict: this agent re-runs in the next batch
-              s_acct[acc++] = t;
-              s_ctl.unused -= 1u;
+              const uint32_t off = lb0 + lane_rank(hb);
+              if (sm != 0u && off < lcap) {
+                slist[2u * off] = sc;
+                slist[2u * off + 1u] = sm;
+                ++sl;
+                sc += bd;
+                seek();
+              }
             }
-            s_cnt2 = acc;
-            s_doit = stop;
-            s_nassign += acc;
-            if (PLAN_DBG) {
-              s_tick[37] += 1;    // batches
-              s_tick[38] += acc;  // agents accepted
+            PBAR();
+            const uint32_t nl = min(s_lcnt, lcap), more = s_more;  // written before the barrier above
+            if (PLAN_DBG && tid == 0) SCAN_COUNT(60, 1);
+            scan_walk(slist, nl, s_apos, s_bestk, P.live, P.klt, (PLAN_DBG && P.sec_ticks) ? P.sec_ticks : nullptr);
+            if (more == 0u) break;  // block-uniform
+            PBAR();  // every thread has read s_lcnt / s_more and its list entries
+            if (tid == 0) s_lcnt = s_more = 0u;
+            PBAR();
+          }
+          SCAN_TICK(50);
+          PBAR();
+          SCAN_TICK(51);
+          PLAN_TICK(34);
+          // Accept in agent order up to the first agent that must stop (past the first bad delivery, out
+          // of tasks) or whose task an earlier batch agent took (it and the rest re-run in the next
+          // batch): one lane of wave 0 per batch agent. Every agent below that first one is accepted, so
+          // "an earlier accepted agent took my task" is "an earlier batch agent's minimum is my task".
+          if (wid == 0) {
+            const bool in = lane < B;
+            const uint64_t key = in ? s_bestk[lane] : ~0ull;
+            const uint32_t t = (uint32_t)(key & 0xFFFFFFFFu), un0 = s_ctl.unused;
+            const bool halt = in && (list[kk + lane] > bad_at || lane >= un0 || key == ~0ull);
+            bool dup = false;
+            for (uint32_t e = 0; e + 1u < B; ++e) {  // wave-uniform
+              const uint32_t te = (uint32_t)__builtin_amdgcn_readlane((int)t, (int)e);
+              dup |= e < lane && te == t;
+            }
+            const uint64_t hm = __ballot(halt), fm = __ballot(in && (halt || dup));
+            const uint32_t acc = fm != 0ull ? (uint32_t)__builtin_ctzll(fm) : B;
+            if (lane < acc) s_acct[lane] = t;
+            if (lane == 0) {
+              s_ctl.unused = un0 - acc;
+              s_cnt2 = acc;
+              s_doit = (acc < B && ((hm >> acc) & 1ull)) ? 1u : 0u;  // this step assigns no more
+              s_nassign += acc;
+              if (PLAN_DBG) {
+                s_tick[37] += 1;    // batches
+                s_tick[38] += acc;  // agents accepted
+              }
             }
           }
           PBAR();
@@ -1560,8 +1657,11 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
           PBAR();
           PLAN_TICK(36);
           if (s_doit) break;  // block-uniform
+#pragma unroll
+          for (uint32_t s = 0; s < KPT; ++s)  // the counts the update above lowered
+            if (tid + s * bd < nch) kc[s] = P.kcnt[tid + s * bd];
           kk += acc;
-          bcur = (kab & 4u) ? 1u : acc == B ? min(ABATCH, 2u * bcur) : max(acc, 1u);
+          bcur = acc == B ? min(wmax, 2u * bcur) : max(acc, 1u);
         }
         if (bad_at != NO_AGENT && !s_bad) {  // block-uniform
           if (tid == 0) {
