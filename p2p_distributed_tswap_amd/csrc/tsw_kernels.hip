@@ -118,7 +118,9 @@ __global__ void __launch_bounds__(1024) k_bfs(DevGrid G, const uint32_t* __restr
       any = __syncthreads_or(any);
       if (!any) break;
       ++level;
-      if (level >= 0xFFFEu) {
+      // this pass found cells at distance `level`: 0xFFFE is the largest a table holds (0xFFFF is DIST_INF, and
+      // what the pass wrote for cells 65,535 steps away), so only a pass that finds cells there is an overflow
+      if (level >= 0xFFFFu) {
         if (tid == 0) atomicOr(err, ERR_DIST_OVERFLOW);
         if (tid == 0 && govf) govf[gi] = 1u;  // planned without a table (K3)
         break;
