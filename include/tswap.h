@@ -153,7 +153,7 @@ uint64_t tsw_build_id(void);
  * (:136), or whose off-grid/blocked delivery is looked up when its agent reaches
  * the pickup (:112). A bad task cell that is never looked up does not fail the
  * call. The nearest-pickup choice uses the raw pickup point (:125-130), its
- * coordinates clamped to 0xFFFE (cannot change the winner: see tsw_capi.hip). */
+ * coordinates clamped to 0xFFFE (cannot change the winner: see plan_impl, tsw_plan_host.hip). */
 int tsw_plan_mapd(tsw_ctx *ctx, const tsw_point *starts, uint32_t n, const tsw_task *tasks,
                   uint32_t m, uint32_t max_t, tsw_rec *out, uint32_t *out_T);
 

@@ -1,6 +1,6 @@
 // tsw_host_astar.h — the exact A* next hop on a host core (plain C++, no HIP): the same astar_one,
 // heap_sift_up and heap_pop as the device (tsw_astar.h, __host__ __device__) run over the host copy of
-// the neighbour masks. Used by the plan dispatch's host service (tsw_capi.hip: the calling thread
+// the neighbour masks. Used by the plan dispatch's host service (tsw_plan_host.hip: the calling thread
 // answers the planner's needed pairs while k_plan runs) and by tsw_host_next_hop_codes.
 #pragma once
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // tsw_internal.h — device-side data layout shared by the HIP kernels and the
-// host context (tsw_capi.hip). gfx950 only.
+// host context (tsw_ctx.h). gfx950 only.
 //
 // HBM layout (per context):
 //   nbmask  [ncell]            u8   bit d (0..3) = neighbour in dir d exists

@@ -144,7 +144,7 @@ hipError_t launch_astar_lds(const DevGrid& G, const AstarQuery* Q, uint32_t nq, 
 // for queries whose byte-encoded g_scores overflowed).
 uint32_t astar_wave_slots(const DevGrid& G, int num_cu, bool global_gs = false);
 bool astar_wave_lds_gs(const DevGrid& G);  // k_astar_wave keeps this grid's g_scores in LDS
-// diagnostics of k_astar_wave (read once per context from the environment, tsw_capi.hip Tunables)
+// diagnostics of k_astar_wave (read once per context from the environment, tsw_ctx.h Tunables)
 constexpr uint32_t ASTAR_DIAG_SERIAL = 1u;  // lone-lane heap core instead of the wave-cooperative one
 constexpr uint32_t ASTAR_DIAG_PROF = 2u;    // per-query pop / clock profile printed to stderr
 hipError_t launch_astar_wave(const DevGrid& G, const AstarQuery* Q, uint32_t nq, uint8_t* nh_base, uint64_t nstride,

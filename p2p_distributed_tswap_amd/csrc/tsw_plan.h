@@ -131,7 +131,7 @@ struct PlanArgs {
   uint32_t* mk;   // per agent batch marks of the wave rules rounds (global copy, n + 1 entries)
   uint32_t* occ;  // per cell occupancy
   uint64_t* mu;   // per cell round-tagged lowest undecided targeting agent (global copy)
-  // K4 spatial index (tsw_capi.hip plan_impl): the tasks in Morton order of their pickup points (coordinates
+  // K4 spatial index (tsw_plan_host.hip plan_impl): the tasks in Morton order of their pickup points (coordinates
   // clamped to 0xFFFE). live[pos] = pickup point (x | y << 16) while unused, TASK_TAKEN once assigned; klt[pos] =
   // the task index; kpos[task] = its position; chunks of KCH positions have a static bounding box kbox
   // (x0 | y0 << 16, x1 | y1 << 16) and a count of untaken entries kcnt. Padding entries are TASK_TAKEN.
@@ -175,7 +175,7 @@ struct PlanArgs {
   // [1] abort (host watchdog: planner waits give up, workers exit), [2] planner heartbeat (timesteps),
   // [3] host A* service: request-ring entries the host has claimed so far (written by the host)
   uint32_t* hflags;
-  // host A* service (coop mode, tsw_capi.hip serve_host_astar): rings of hring entries (a power of two;
+  // host A* service (coop mode, tsw_plan_host.hip host_serve_one): rings of hring entries (a power of two;
   // 0 = service off) in mapped coherent host memory. A planner thread waiting for a needed pair takes
   // ticket t (0, 1, ... per launch) and stores seq << 40 | v << 20 | goal into hreq[t % hring] with
   // seq = t + 1: one 64-bit system-scope store carries the whole request, so no head word and no

@@ -31,7 +31,7 @@ def morton(x, y):
 
 
 class Index:
-    """The host's K4 index (tsw_capi.hip plan_impl): live[pos] = pickup point or TAKEN, klt[pos] = task,
+    """The host's K4 index (tsw_plan_host.hip plan_impl): live[pos] = pickup point or TAKEN, klt[pos] = task,
     kbox[chunk] = static bounding box, kcnt[chunk] = untaken entries; the tail chunk is padded with TAKEN."""
 
     def __init__(self, picks, kch=KCH):
