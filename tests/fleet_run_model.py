@@ -60,6 +60,34 @@ def goal_op_rounds(act, partner, part_off, part):
     return rounds
 
 
+def goal_op_pending(act, partner, part_off, part):
+    """The claim scheme of tsw_fleet.hip round by round: the pending ops (initiators, ascending) at the
+    start of every round. An op fires when it is the smallest pending op on every agent it touches; the
+    others stay pending, in order. len(result) == goal_op_rounds(...)."""
+    act = np.asarray(act)
+    cur = [int(i) for i in np.flatnonzero((act == SWAP) | (act == ROTATION))]
+    rounds = []
+    while cur:
+        rounds.append(cur)
+        owner = {}
+        for i in cur:
+            for a in touched(i, act, partner, part_off, part):
+                owner[a] = min(owner.get(a, i), i)
+        cur = [i for i in cur if any(owner[a] != i for a in touched(i, act, partner, part_off, part))]
+    return rounds
+
+
+def kept_carry_rounds(act, partner, part_off, part, chunk=256):
+    """Rounds in which k_fleet_goals' compaction (chunks of `chunk` pending ops, `kept += total` between
+    them) places a kept op of a later chunk behind kept ops of an earlier one: kept > 0 at k0 > 0."""
+    pend = goal_op_pending(act, partner, part_off, part)
+    count = 0
+    for cur, nxt in zip(pend, pend[1:]):
+        keep = np.isin(cur, nxt)
+        count += bool(keep[:chunk].any() and keep[chunk:].any())
+    return count
+
+
 def run_model(og, rows, v, g, radius, ticks):
     """`ticks` ticks of brute_nearby + oracle_fleet + apply_model with the fixed-point stop (a tick that
     changes nothing ends the run and is not counted). Returns (v, g, v_rec, g_rec, ticks_done, decisions):
@@ -79,6 +107,35 @@ def run_model(og, rows, v, g, radius, ticks):
         vr.append(v.copy())
         gr.append(g.copy())
     return v, g, np.stack(vr, axis=1), np.stack(gr, axis=1), len(dec), dec
+
+
+@functools.lru_cache(maxsize=None)
+def long_run_case(ticks=3):
+    """The model run of fc.long_rules123() at r = 80 (lists of 1,099 entries), cut where the library must
+    stop: the first tick in which an agent's decision goes past Rule 3 (Rotation or Wait) reaches Rule 4
+    with a list over the 1,024-entry limit, so that tick fails with TSW_EOVERFLOW and is not applied.
+    Returns (v, g, v_rec, g_rec, ticks_done, overflow): the state and the records after ticks_done ticks,
+    overflow True when tick number ticks_done is the failing one. Computed once and shared (do not modify)."""
+    from oracle import OracleGraph
+
+    rows, v, g, _ = fc.long_rules123()
+    og = OracleGraph(maps.rows_to_array(rows))
+    v, g = v.copy(), g.copy()
+    vr, gr = [v.copy()], [g.copy()]
+    overflow = False
+    for _ in range(ticks):
+        off, idx = fc.brute_nearby(v, len(rows[0]), 80)
+        d = fc.oracle_fleet(og, v, g, off, idx)
+        if (d[0] >= ROTATION).any():
+            overflow = True
+            break
+        v1, g1 = apply_model(v, g, *d)
+        if np.array_equal(v1, v) and np.array_equal(g1, g):
+            break
+        v, g = v1, g1
+        vr.append(v.copy())
+        gr.append(g.copy())
+    return v, g, np.stack(vr, axis=1), np.stack(gr, axis=1), len(vr) - 1, overflow
 
 
 @functools.lru_cache(maxsize=None)
@@ -147,11 +204,29 @@ def apply_case(name):
         n = 80
         order = [int(x) for x in np.random.RandomState(70).permutation(np.arange(1, n))[:70]]
         return _case(o16, np.arange(n), np.arange(n) + 100, [(0, ROTATION, order), (5, SWAP, 6)])
+    # more than 256 pending ops that do NOT fire: the compaction of the kept ops crosses its chunks of 256
+    if name == "chain300":  # as chain200: round 1 keeps 299 ops, every round all but one
+        o32 = maps.open_map(32, 32)
+        n = 301
+        return _case(o32, np.arange(n), np.arange(n)[::-1] + 20, [(i, SWAP, 0) for i in range(1, n)])
+    if name == "pairs800":  # 400 partners with two requesters each: round 1 fires every even op of 800, keeps the odd
+        o64 = maps.open_map(64, 64)
+        n = 1200
+        ops = [(3 * k + d, SWAP, 3 * k + 2) for k in range(400) for d in (0, 1)]
+        return _case(o64, np.arange(n), (np.arange(n) * 7 + 3) % 4096, ops)  # 7 is odd: the goals are distinct
+    if name == "rotations_kept300":  # 300 rotations {0, 300 + i} by initiator i, all through agent 0; 4 far swaps
+        o32 = maps.open_map(32, 32)
+        n = 620
+        ops = [(i, ROTATION, [0, 300 + i]) for i in range(1, 301)]
+        ops += [(604 + 4 * k, SWAP, 606 + 4 * k) for k in range(4)]
+        return _case(o32, np.arange(n), (np.arange(n) * 5 + 1) % 1024, ops)
     raise KeyError(name)
 
 
 APPLY_CASES = ["two_requesters", "rotation_3cycle", "rotation_then_swap", "swap_then_rotation", "two_moves_one_cell",
-               "chain200", "disjoint1500", "rotation70"]
+               "chain200", "disjoint1500", "rotation70", "chain300", "pairs800", "rotations_kept300"]
+# the cases above whose kept ops fill more than one chunk of the compaction
+KEPT_CASES = ["chain300", "pairs800", "rotations_kept300"]
 
 
 def single_agent():

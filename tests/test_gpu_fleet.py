@@ -1,6 +1,8 @@
 """GPU: the fleet-wide decentralized tick. tsw_nearby against the brute-force definition of the lists,
 tsw_decide_fleet bit-exact against the CPU oracle's compute_next_move_with_tswap (agent.rs:329-462) run
-per agent on its brute-force list, and the documented error codes."""
+per agent on its brute-force list, and the documented error codes. The shapes of fleet_cases.py put both
+on their internal boundaries: diamonds taller than the 64 rows a wave takes per trip, 2,048-element scan
+tiles (one, one and a bit, 256, 257), lists of exactly 1,024 entries and one more."""
 import ctypes
 import functools
 
@@ -111,15 +113,28 @@ def test_nearby_rejects_off_grid_cell(planners):
     assert np.array_equal(off, fc.brute_case("open6", 2)[0]) and np.array_equal(idx, fc.brute_case("open6", 2)[1])
 
 
+def test_nearby_half_million_agents_matches_grouping(planners):
+    """2,048 * 256 + 2 agents: the offsets' scan has 257 tiles, so k_scan_sums takes a second trip with its
+    carry. r = 0 on a fleet with up to three agents per cell, against the grouping reference (proven against
+    brute force on the CPU); nb_off and nb_idx compared whole."""
+    W, H, rows, v = fc.crowd_fleet()
+    boff, bidx = fc.grouped_nearby(v)
+    rc, off, idx, total = _raw_nearby(planners(rows), v, 0, bidx.size)
+    assert rc == TSW_OK and total == bidx.size
+    assert np.array_equal(off, boff), _first_diff(off, boff)
+    assert np.array_equal(idx, bidx), _first_diff(idx, bidx)
+
+
 # ---- fleet decide vs the oracle -----------------------------------------------------------------------
 
-@pytest.mark.parametrize("name,r", [("rand20", 15), ("rand20", 3), ("dense12", 2), ("warehouse", 15)])
+# tall9x200 at r = 40: diamonds of 81 rows, so the fill that writes nb_v / nb_g walks two chunks of rows
+@pytest.mark.parametrize("name,r", [("rand20", 15), ("rand20", 3), ("dense12", 2), ("warehouse", 15), ("tall9x200", 40)])
 def test_decide_fleet_matches_oracle(planners, name, r):
     rows, v, g = fc.fleet_case(name)
     ref = _oracle(name, r)
     got = planners(rows).decide_fleet(v, g, r)
     _assert_fleet_equal(got, ref)
-    if name in ("rand20", "warehouse"):
+    if name in ("rand20", "warehouse", "tall9x200"):
         assert set(np.unique(ref[0]).tolist()) == {0, 1, 2, 3}
     assert ref[3][-1] > 0  # rotations, so the participant translation is exercised
 
@@ -136,6 +151,72 @@ def test_decide_fleet_equals_decide_on_nearby_lists(planners):
         assert (a, c) == (act[i], cell[i]), i
         assert partner[i] == (0xFFFFFFFF if pt == 0xFFFFFFFF else li[pt]), i
         assert [int(li[k]) for k in ps] == part[part_off[i]:part_off[i + 1]].tolist(), i
+
+
+# ---- lists of exactly 1,024 entries, and of 1,025 ------------------------------------------------------
+
+NONE = 0xFFFFFFFF
+
+
+def _raw_decide(p, v, g, off, idx):
+    """tsw_decide on the lists (off, idx) of agent indices. Returns (rc, act, cell, partner, npart, part) in
+    tsw_decide's own form: list indices, agent i's participants at part[off[i] + i ..]."""
+    n = v.size
+    nv, ng = np.ascontiguousarray(v[idx]), np.ascontiguousarray(g[idx])
+    act, cell, partner, npart = (np.full(n, 0xDEADBEEF, dtype=np.uint32) for _ in range(4))
+    part = np.zeros(idx.size + n + 1, dtype=np.uint32)
+    rc = p._lib.tsw_decide(p._ctx, _p(v), _p(g), n, _p(off), _p(nv), _p(ng), _p(act), _p(cell), _p(partner), _p(npart),
+                           _p(part))
+    return rc, act, cell, partner, npart, part
+
+
+def test_cap1025_decides_at_the_full_list_length(planners):
+    """1,025 agents that all see each other: every list has 1,024 entries, the LDS sort's last slot and
+    Rule 4's whole `chased` mask in use (rotations through agents >= 1,000). TSW_OK, equal to the oracle."""
+    rows, v, g = fc.cap_fleet(1025)
+    rc, act, cell, partner, off, part = _raw_fleet(planners(rows), v, g, 80, 8192)
+    assert rc == TSW_OK
+    _assert_fleet_equal((act, cell, partner, off, part[:off[-1]]), fc.cap_oracle(1025))
+
+
+def test_cap1025_decide_fleet_equals_decide_on_nearby_lists(planners):
+    rows, v, g = fc.cap_fleet(1025)
+    p = planners(rows)
+    off, idx = p.nearby(v, 80)
+    assert np.all(np.diff(off.astype(np.int64)) == 1024)
+    rc, act, cell, par, npart, lpart = _raw_decide(p, v, g, off, idx)
+    assert rc == TSW_OK
+    fact, fcell, fpartner, fpart_off, fpart = p.decide_fleet(v, g, 80)
+    base = off[:-1].astype(np.int64)
+    partner = np.where(par == NONE, NONE, idx[base + np.where(par == NONE, 0, par)]).astype(np.uint32)
+    for name, a, b in (("act", act, fact), ("cell", cell, fcell), ("partner", partner, fpartner),
+                       ("npart", npart, np.diff(fpart_off))):
+        assert np.array_equal(a, b), f"{name}: first difference at {_first_diff(a, b)}"
+    assert npart.sum() > 0
+    for i in np.flatnonzero(npart):
+        lp = lpart[off[i] + i:off[i] + i + npart[i]]
+        assert np.array_equal(idx[base[i] + lp], fpart[fpart_off[i]:fpart_off[i + 1]]), int(i)
+
+
+def test_cap1026_is_overflow_and_cap1025_decides_afterwards(planners):
+    """One more agent: lists of 1,025 entries, one past the limit of Rule 4 -> TSW_EOVERFLOW; the same
+    context then decides the 1,025-agent fleet."""
+    rows, v, g = fc.cap_fleet(1026)
+    p = planners(rows)
+    rc = _raw_fleet(p, v, g, 80, 8192)[0]
+    assert rc == TSW_EOVERFLOW
+    assert "1024" in p._lib.tsw_last_error(p._ctx).decode()
+    _, v5, g5 = fc.cap_fleet(1025)
+    _assert_fleet_equal(p.decide_fleet(v5, g5, 80), fc.cap_oracle(1025))
+
+
+def test_long_lists_decided_by_rules_1_to_3_match_oracle(planners):
+    """1,100 agents with lists of 1,099 entries, none of which goes past Rule 3: tsw_decide_fleet decides
+    on the nb_v / nb_g the brute-force fill wrote, and translates the swap partners through its nb_idx."""
+    rows, v, g, ref = fc.long_rules123()
+    rc, act, cell, partner, off, part = _raw_fleet(planners(rows), v, g, 80, 64)
+    assert rc == TSW_OK
+    _assert_fleet_equal((act, cell, partner, off, part[:off[-1]]), ref)
 
 
 # ---- overflow and errors ------------------------------------------------------------------------------

@@ -80,6 +80,11 @@ def test_apply_matches_model_on_hand_made_cases(planners, name):
     ref_v, ref_g = fm.apply_model(v, g, *dec)
     got_v, got_g = planners(rows).fleet_apply(v, g, *dec)
     _assert_state(got_v, got_g, ref_v, ref_g)
+    if name in fm.KEPT_CASES:  # kept ops in more than one chunk of the compaction: no give-up, and an effect
+        rc, raw_v, raw_g = _raw_apply(planners(rows), v, g, *dec)
+        assert rc == TSW_OK  # FLEET_STUCK would be TSW_EHIP
+        assert np.array_equal(raw_v, v) and not np.array_equal(raw_g, g)
+        _assert_state(raw_v, raw_g, ref_v, ref_g)
 
 
 @pytest.mark.parametrize("name,r,ticks", fm.RUN_CASES)
@@ -210,6 +215,26 @@ def test_list_past_the_limit_reaching_rule4_is_overflow(planners):
     _assert_state(v1, g1, v, g)
     v1, g1, done = p.fleet_run(v, g, 1, 5)  # below the limit the same fleet runs
     assert done == 1 and v1[0] == v[0]  # agent 0 waits (Rule 5 finds nobody at its cell), the others move
+
+
+def test_long_lists_run_on_rules_1_to_3_until_the_model_reaches_rule4(planners):
+    """1,100 agents at r = 80 whose first tick is decided by Rules 1-3 alone: the run's ticks go through the
+    brute-force fill's nb_v / nb_g. Three ticks equal the model's, unless the model says that an earlier
+    tick reaches Rule 4 (lists of 1,099 entries: over the limit): then TSW_EOVERFLOW at exactly that tick,
+    with the state and the records of the ticks before it."""
+    rows, v, g, _ = fc.long_rules123()
+    ref_v, ref_g, ref_vr, ref_gr, ref_done, overflow = fm.long_run_case(3)
+    p = planners(rows)
+    rc, v1, g1, done, vr, gr = _raw_run(p, v, g, 80, 3)
+    if overflow:
+        assert rc == TSW_EOVERFLOW and "1024" in p._lib.tsw_last_error(p._ctx).decode()
+    else:
+        assert rc == TSW_OK
+    assert done == ref_done
+    assert np.array_equal(vr[:, :done + 1], ref_vr), "v_rec: " + _first_diff(vr[:, :done + 1], ref_vr)
+    assert np.array_equal(gr[:, :done + 1], ref_gr), "g_rec: " + _first_diff(gr[:, :done + 1], ref_gr)
+    assert np.all(vr[:, done + 1:] == FILL) and np.all(gr[:, done + 1:] == FILL)
+    _assert_state(v1, g1, ref_v, ref_g)
 
 
 def _invalid_decisions():
