@@ -499,8 +499,13 @@ static int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
                 "scanning waves %llu list rounds %llu | batch widths 1: %llu 2-4: %llu 5-8: %llu 9-16: %llu\n",
                 tk[48] / 100.0, tk[49] / 100.0, tk[50] / 100.0, tk[51] / 100.0, tk[52], tk[53], tk[54], tk[60], tk[55], tk[56],
                 tk[57], tk[58]);
-        fprintf(stderr, "[k_plan] PRE1 publish us %.0f (%llu) | rules init us %.0f prefetch us %.0f publish us %.0f (%llu)\n",
-                tk[24] / 100.0, tk[25], tk[26] / 100.0, tk[27] / 100.0, tk[28] / 100.0, tk[29]);
+        // walk-ahead (round 14): steps whose walk ran in PRE1 / that PRE1 left to the rules phase / whose walk the
+        // waves beside wave 0 finished and published there (counted by the publishing wave), those walkers' time
+        // from arming to the last wave's count, steps in which wave 0 was done before them
+        fprintf(stderr, "[k_plan] PRE1 publish us %.0f (%llu) | rules init us %.0f prefetch us %.0f publish us %.0f (%llu)"
+                " | walk-ahead steps in PRE1 %llu left to RULES %llu done in RULES %llu walkers us %.0f wave 0 first %llu\n",
+                tk[24] / 100.0, tk[25], tk[26] / 100.0, tk[27] / 100.0, tk[28] / 100.0, tk[29], tk[45], tk[46], tk[62],
+                tk[61] / 100.0, tk[47]);
         fprintf(stderr, "[k_plan] wave rules kcycles: load %.0f stale %.0f fast %.0f update %.0f slow %.0f rot %.0f | "
                 "loads %llu fast firings %llu | rotations %llu, settle kcycles: successors %.0f walk %.0f\n",
                 tk[16] / 1e3, tk[17] / 1e3, tk[18] / 1e3, tk[19] / 1e3, tk[20] / 1e3, tk[21] / 1e3, tk[22], tk[23],
