@@ -194,7 +194,7 @@ struct tsw_ctx {
   DevBuf<uint32_t> d_pred;    // TSW_PLAN_DEBUG: per-agent last predicted task
   DevBuf<uint4> d_wf;         // per-agent walk-ahead frontier (PlanArgs::wf)
   uint32_t qt_count = 0;
-  // coherent, mapped (.dev: PlanArgs::hflags): [0] planner resident, [1] abort, [2] heartbeat, [8..23] PBAR
+  // coherent, mapped (.dev: PlanArgs::hflags): HF_WORDS words, named by HostFlag (tsw_plan.h)
   PinnedBuf<uint32_t> h_flags;
   uint64_t coop_aborts = 0;
   uint32_t watchdog_ms = 10000;  // tsw_opts.watchdog_ms
@@ -340,6 +340,13 @@ int grow_synced(tsw_ctx* c, DevBuf<T>& b, size_t need) {
   HIPCHK(hipStreamSynchronize(c->s));
   HIPCHK(b.grow(need));
   return TSW_OK;
+}
+
+// Morton (Z-order) key of a point: the low 16 bits of x and y interleaved, x in the even bits.
+inline uint32_t morton2(uint32_t x, uint32_t y) {
+  uint32_t z = 0;
+  for (uint32_t b = 0; b < 16u; ++b) z |= ((x >> b) & 1u) << (2u * b) | ((y >> b) & 1u) << (2u * b + 1u);
+  return z;
 }
 
 struct Timer {

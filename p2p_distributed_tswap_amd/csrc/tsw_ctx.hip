@@ -295,13 +295,13 @@ tsw_ctx* tsw_create(const uint8_t* cells, uint32_t w, uint32_t h, const tsw_opts
   if ((e = c->h_stat.alloc(1)) != hipSuccess) return fail("pinned status", e);
   if ((e = c->d_ctl.alloc(1)) != hipSuccess) return fail("malloc ctl", e);
   if ((e = c->d_pargs.alloc(1)) != hipSuccess) return fail("malloc plan args", e);
-  if ((e = c->d_ticks.alloc(64)) != hipSuccess) return fail("malloc ticks", e);
-  if ((e = hipMemsetAsync(c->d_ticks, 0, 64 * sizeof(unsigned long long), c->s)) != hipSuccess)
+  if ((e = c->d_ticks.alloc(TK_COUNT)) != hipSuccess) return fail("malloc ticks", e);
+  if ((e = hipMemsetAsync(c->d_ticks, 0, TK_COUNT * sizeof(unsigned long long), c->s)) != hipSuccess)
     return fail("memset ticks", e);
   hipDeviceGetAttribute(&c->wall_khz, hipDeviceAttributeWallClockRate, c->device);
   if (c->wall_khz <= 0) c->wall_khz = 100000;
   if ((e = c->h_ctl.alloc(1)) != hipSuccess) return fail("pinned ctl", e);
-  if ((e = c->h_flags.alloc(64, MAPPED)) != hipSuccess) return fail("pinned flags", e);
+  if ((e = c->h_flags.alloc(HF_WORDS, MAPPED)) != hipSuccess) return fail("pinned flags", e);
   if ((e = c->h_flags.map()) != hipSuccess) return fail("flags device pointer", e);
   if (c->host_threads) {
     uint32_t ring = HOST_RING_ENTRIES;
@@ -345,13 +345,13 @@ int tsw_get_stats(const tsw_ctx* c, tsw_stats* out) {
   if (!c || !out) return TSW_EINVAL;
   tsw_ctx* cc = const_cast<tsw_ctx*>(c);
   resolve_timing(cc);
-  unsigned long long ticks[8] = {0};
+  unsigned long long ticks[TK_SECTIONS] = {0};
   if (hipSetDevice(c->device) == hipSuccess && hipStreamSynchronize(c->s) == hipSuccess)
     (void)hipMemcpy(ticks, c->d_ticks, sizeof ticks, hipMemcpyDeviceToHost);
   *out = c->st;
   out->tables = c->tab_live;
   out->table_evictions = c->evictions;
-  for (int k = 0; k < 8; ++k) out->plan_section_ms[k] = (double)ticks[k] / (double)c->wall_khz;
+  for (int k = 0; k < TK_SECTIONS; ++k) out->plan_section_ms[k] = (double)ticks[k] / (double)c->wall_khz;
   return TSW_OK;
 }
 
@@ -362,7 +362,7 @@ int tsw_reset_stats(tsw_ctx* c) {
   const uint64_t tabs = c->st.tables;
   c->st = tsw_stats{};
   c->st.tables = tabs;
-  if (c->d_ticks) (void)hipMemsetAsync(c->d_ticks, 0, 64 * sizeof(unsigned long long), c->s);
+  if (c->d_ticks) (void)hipMemsetAsync(c->d_ticks, 0, TK_COUNT * sizeof(unsigned long long), c->s);
   return TSW_OK;
 }
 

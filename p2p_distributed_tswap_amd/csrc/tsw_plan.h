@@ -1,11 +1,14 @@
 // tsw_plan.h — arguments and resumable control block of the persistent plan kernel.
 #pragma once
+#include <chrono>
 #include <cstddef>
 
 #include "tsw_internal.h"
+#include "tswap.h"
 
-// The host A* request ring's word layout and match test are plain C++ (tests/host/host_ask_match_main.cpp
-// builds them with the host compiler alone); everything below them needs HIP.
+// What the planner and the host share by convention alone is plain C++ and comes first (tests/host/*.cpp build it
+// with the host compiler alone): the host A* request ring's word layout and match test, the slots of
+// PlanArgs::hflags and PlanArgs::sec_ticks, the watchdog rule and the error table. Everything below needs HIP.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define TSW_RING_HD __host__ __device__ __forceinline__
@@ -47,6 +50,129 @@ TSW_RING_HD bool host_reply_match(unsigned long long w, uint32_t r, uint32_t v, 
   if ((r >> 8) != (uint32_t)(w >> 40) || (r & 0xFFu) > NH_STAY) return false;
   *code = (uint8_t)(r & 0xFFu);
   return true;
+}
+
+// ---- PlanArgs::hflags: host-visible (pinned, system-coherent) words, cleared by the host before every dispatch ----
+enum HostFlag : int {
+  HF_RESIDENT = 0,      // set by the planner block once it runs; nothing reads it
+  HF_ABORT = 1,         // host watchdog: planner waits give up, its round loops exit with ERR_ABORT, workers leave
+  HF_HEARTBEAT = 2,     // the planner's timestep count (PlanCtl::steps_run), stored at every step end
+  HF_HOST_TAIL = 3,     // host A* service: request-ring entries the host has claimed so far (written by the host)
+  HF_BAR_MISMATCH = 4,  // -DTSW_PBAR: first barrier mismatch, wave 0's line << 16 | the other wave's
+  HF_BAR_LINE = 8,      // -DTSW_PBAR, + wave: the barrier's line, | 0x10000 once passed
+  HF_BAR_COUNT = 24,    // -DTSW_PBAR, + wave: barriers passed
+  HF_WORDS = 40,
+};
+constexpr int PLAN_WAVES_MAX = 16;  // waves of the planner block (PLAN_BLOCK_MAX / 64): the per-wave words above
+
+// ---- PlanArgs::sec_ticks: the planner's diagnostic slots (TSW_PLAN_DEBUG), named for what k_plan writes ----------
+// Ticks are wall-clock ticks (100 MHz) unless they say shader cycles. The first TK_STICK_COUNT slots are
+// accumulated in LDS (k_plan's s_tick) and added at the planner's exit, the others are added to in place.
+enum TickSlot : int {
+  TK_SECTION = 0,  // + SEC_* (7: entry / copy-in): ticks per section
+  TK_SECTIONS = 8,
+  TK_MOVE_PASS1 = 8,      // movement rounds: ticks of the three passes
+  TK_R3_WALK_HOPS = 9,    // rules: hops of rule 3's cycle walks
+  TK_MOVE_PASS2 = 10,
+  TK_R4_ROTATIONS = 11,   // rules: rule-4 rotations
+  TK_MOVE_PASS3 = 12,
+  TK_RULES_SCAN = 13,     // rules rounds: ticks of the scan, the firing, the relabel
+  TK_RULES_FIRE = 14,
+  TK_RULES_RELABEL = 15,
+  TK_WR_LOAD = 16,        // wave rules rounds: shader cycles per part of the loop
+  TK_WR_STALE = 17,
+  TK_WR_FAST = 18,
+  TK_WR_UPDATE = 19,
+  TK_WR_SLOW = 20,
+  TK_WR_ROT = 21,
+  TK_WR_LOADS = 22,         // ... chunk loads
+  TK_WR_FAST_FIRINGS = 23,  // ... firings on the batched / fast path
+  TK_PRE1_PUBLISH = 24,     // PRE1: ticks and count of coop_publish
+  TK_PRE1_PUBLISHES = 25,
+  TK_RULES_INIT = 26,       // rules start: ticks of rules_init, rules_prefetch, coop_publish, and its count
+  TK_RULES_PREFETCH = 27,
+  TK_RULES_PUBLISH = 28,
+  TK_RULES_PUBLISHES = 29,
+  TK_SETTLE_SUCC = 30,      // rules settle: shader cycles of the successors pass and the walk
+  TK_SETTLE_WALK = 31,
+  TK_ASG_TRANSITIONS = 32,  // ASSIGN: ticks per part
+  TK_ASG_COMPACT = 33,
+  TK_ASG_SCAN = 34,
+  TK_ASG_ACCEPT = 35,
+  TK_ASG_UPDATE = 36,
+  TK_ASG_BATCHES = 37,      // ... batches, agents accepted, sections
+  TK_ASG_ACCEPTED = 38,
+  TK_ASG_SECTIONS = 39,
+  TK_WB_MARKS = 40,         // wave rules batches: shader cycles of marks, walks, apply
+  TK_WB_WALKS = 41,
+  TK_WB_APPLY = 42,
+  TK_WB_BATCHES = 43,       // ... batches, the sum of their longest walks (hops)
+  TK_WB_HOPS = 44,
+  TK_WALK_IN_PRE1 = 45,     // step-start walk-ahead: steps walked in PRE1 / left to the rules phase
+  TK_WALK_LEFT = 46,
+  TK_WALK_WAVE0_FIRST = 47, // ... steps in which wave 0 was done before the walkers
+  TK_STICK_COUNT = 48,
+  TK_SCAN_INDEX = 48,       // K4 scan: ticks of its parts (the index part is no longer written)
+  TK_SCAN_BOUND = 49,
+  TK_SCAN_ENTRIES = 50,
+  TK_SCAN_REDUCE = 51,
+  TK_SCAN_PAIRS = 52,       // ... chunk-agent pairs, chunks, waves with an entry
+  TK_SCAN_CHUNKS = 53,
+  TK_SCAN_WAVES = 54,
+  TK_SCAN_B_ONE = 55,       // ... batches of 1, 2-4, 5-8, more agents
+  TK_SCAN_B_LE4 = 56,
+  TK_SCAN_B_LE8 = 57,
+  TK_SCAN_B_MORE = 58,
+  TK_SCAN_ROUNDS = 60,      // ... rounds over the list
+  TK_WALKERS = 61,          // walk-ahead on the rules rounds' idle waves: ticks from arming to the last wave's count
+  TK_WALK_IN_RULES = 62,    // ... steps whose walk they finished
+  TK_COUNT = 64,
+};
+
+// ---- the watchdog rule of one dispatch -----------------------------------------------------------------------
+// The planner publishes its timestep count (HF_HEARTBEAT). If it stops moving for more than watchdog_ms while
+// the dispatch runs, the host raises HF_ABORT, once: check() says when. A heartbeat that moves re-arms the
+// timer but not the latch, and an abort word that is already set never fires again.
+struct PlanWatchdog {
+  using Clock = std::chrono::steady_clock;
+  std::chrono::milliseconds limit;
+  uint32_t last;
+  Clock::time_point seen;
+  bool fired = false;
+  PlanWatchdog(uint32_t watchdog_ms, uint32_t heartbeat, Clock::time_point now)
+      : limit(watchdog_ms), last(heartbeat), seen(now) {}
+  bool check(uint32_t heartbeat, uint32_t abort_word, Clock::time_point now) {
+    if (heartbeat != last) {
+      last = heartbeat;
+      seen = now;
+      return false;
+    }
+    if (fired || abort_word || !(now - seen > limit)) return false;
+    fired = true;
+    return true;
+  }
+};
+
+// ---- PlanCtl::err -> return code -----------------------------------------------------------------------------
+// Tested in this order: the first row sharing a bit with err gives the call's code. msg: the fixed error
+// string; nullptr where the host composes one (the stopped planner's position, the raw bits).
+struct PlanErrRow {
+  uint32_t bits;
+  int code;
+  const char* msg;
+};
+constexpr PlanErrRow PLAN_ERR_TABLE[] = {
+    {ERR_ABORT, TSW_EINVAL, nullptr},
+    {ERR_BAD_PICKUP, TSW_EINVAL, "assigned task's pickup is off-grid or blocked (reference panics at tswap.rs:136)"},
+    {ERR_BAD_DELIVERY, TSW_EINVAL,
+     "reached pickup's task delivery is off-grid or blocked (reference panics at tswap.rs:112)"},
+    {ERR_NO_TABLE, TSW_EINVAL, nullptr},
+    {0xFFFFFFFFu, TSW_EOVERFLOW, nullptr},
+};
+inline const PlanErrRow* plan_err_row(uint32_t err) {  // nullptr: no error
+  for (const PlanErrRow& r : PLAN_ERR_TABLE)
+    if (err & r.bits) return &r;
+  return nullptr;
 }
 
 }  // namespace tsw
@@ -151,8 +277,7 @@ struct PlanArgs {
   uint64_t* rec;
   uint32_t* grec;
   PlanCtl* ctl;
-  unsigned long long* sec_ticks;  // [64] wall-clock ticks per section [0..7], sub-phase ticks and counters [8..47] (diagnostics);
-                                  // [48..63]: K4 scan parts and counters, added to in place (diagnostics)
+  unsigned long long* sec_ticks;  // [TK_COUNT] diagnostics: ticks per section, sub-phase ticks and counters (TickSlot)
   uint32_t dbg;                   // sub-phase ticks on (TSW_PLAN_DEBUG)
   uint32_t* dtag;                 // diagnostics (TSW_PLAN_DEBUG): per agent, what changed it since PRE1 (CoopCtl::dbg_tag)
   // coop mode: K3 runs concurrently in the dispatch's worker workgroups (tsw_worker.h); Q is the needed queue (qcap entries for the
@@ -171,10 +296,7 @@ struct PlanArgs {
   uint32_t* pred;       // diagnostics (TSW_PLAN_DEBUG): per agent, the task last predicted for it
   uint4* wf;            // per agent: step-start walk-ahead frontier (cell at the walk, goal, stopping cell, its hop); nullptr: off
   CoopCtl* cc;
-  // host-visible (pinned, system-coherent) words: [0] set when the planner block is resident,
-  // [1] abort (host watchdog: planner waits give up, workers exit), [2] planner heartbeat (timesteps),
-  // [3] host A* service: request-ring entries the host has claimed so far (written by the host)
-  uint32_t* hflags;
+  uint32_t* hflags;  // [HF_WORDS] host-visible (pinned, system-coherent) words (HostFlag)
   // host A* service (coop mode, tsw_plan_host.hip host_serve_one): rings of hring entries (a power of two;
   // 0 = service off) in mapped coherent host memory. A planner thread waiting for a needed pair takes
   // ticket t (0, 1, ... per launch) and stores seq << 40 | v << 20 | goal into hreq[t % hring] with
@@ -240,7 +362,7 @@ struct WorkerArgs {
   uint32_t tmask;     // workers with (blockIdx & tmask) == tmask also take task-chain jobs
   uint32_t preempt;   // chain workers serve queued needed / speculative pairs between hops
   uint32_t chain_hops;  // hops a chain worker resolves per task chain (0: the whole pickup -> delivery path)
-  const uint32_t* hflags;  // host watchdog words (hflags[1] = abort)
+  const uint32_t* hflags;  // host watchdog words (HF_ABORT)
   uint32_t* gs_all;   // per-wave global g-score slots (tier 2 / tier 3), ncell u32 each
   uint32_t* epochs;   // per-slot tag epochs
   uint64_t* heaps;    // per-wave global heaps (tier 3), ghcap entries each

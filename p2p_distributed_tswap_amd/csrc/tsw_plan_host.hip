@@ -41,8 +41,8 @@ static int ensure_agents(tsw_ctx* c, size_t n) {
   return TSW_OK;
 }
 
-// Coop-mode buffers: control block, speculative queue, the needed queue sized for a whole launch,
-// the second stream and the host-visible "planner resident" flag.
+// Coop-mode buffers: the A* scratch, the needed queue sized for a whole launch, the control block and
+// the speculative queue.
 static int ensure_coop(tsw_ctx* c, uint32_t n, uint32_t max_t = 0) {
   TRY(ensure_astar_scratch(c));
   // the needed queue is linear over a coop launch too (urgent walk-ahead pairs join it): sized by the plan
@@ -68,6 +68,33 @@ template <class T>
 static T* per_agent(tsw_ctx* c, DevBuf<T>& b, uint32_t n, int fill) {
   if (b.cap < n) (void)b.alloc(n);
   return b.p && hipMemsetAsync(b.p, fill, (size_t)n * sizeof(T), c->s) == hipSuccess ? b.p : nullptr;
+}
+
+// What of the planner's state lives in LDS, in priority order: agents, occupancy grid, task table.
+static void choose_plan_lds(const tsw_ctx* c, PlanArgs* Pp) {
+  PlanArgs& P = *Pp;
+  const size_t budget = (size_t)std::max(c->max_lds - 2048, 0);
+  bool ag = plan_lds_bytes(P.n, P.ncell, P.m, true, false, false) <= budget;
+  // without the whole set, single agent arrays in priority order (PART_*: the rules phase's serial
+  // successor walks and firing scans read SUCC / ONC / V / G; wh10k rules 3.9 -> ? s), then the rules
+  // relabel's pointer-doubling buffers
+  uint32_t part = 0;
+  if (!ag)
+    for (uint32_t bit : {PART_SUCC, PART_ONC, PART_V, PART_G, PART_NHC, PART_CANDC, PART_GT})
+      if ((c->tun.part_lds & bit) && plan_lds_bytes(P.n, P.ncell, P.m, false, false, false, false, true, part | bit) <= budget)
+        part |= bit;
+  bool fl = !ag && c->tun.flinks_lds && plan_lds_bytes(P.n, P.ncell, P.m, false, false, false, true, true, part) <= budget;
+  // the occupancy grid with the movement rounds' MU words, else OCC alone (every rules round reads
+  // OCC: C3's 170x84 fits OCC but not MU beside the agent arrays)
+  bool mu = P.n < 65535u && plan_lds_bytes(P.n, P.ncell, P.m, ag, true, false, fl, true, part) <= budget;  // MU32: 16-bit agent ids
+  bool oc = mu || (c->tun.occ_split && plan_lds_bytes(P.n, P.ncell, P.m, ag, true, false, fl, false, part) <= budget);
+  const bool tk = false;  // K4 reads its spatial index from global memory (the chunks it needs only)
+  P.part_lds = part;
+  P.f_lds = fl;
+  P.mu_lds = mu;
+  P.agents_lds = ag;
+  P.occ_lds = oc;
+  P.tasks_lds = tk;
 }
 
 static PlanArgs plan_args(tsw_ctx* c, uint32_t n, uint32_t m, uint32_t mode, bool want_goals) {
@@ -105,7 +132,7 @@ static PlanArgs plan_args(tsw_ctx* c, uint32_t n, uint32_t m, uint32_t mode, boo
   P.wide_prefetch = c->tun.wide_prefetch;
   P.wide_hi = c->tun.wide_hi ? c->tun.wide_hi : c->tun.wide_prefetch;
   P.wide_lo = c->tun.wide_lo;
-  P.spec_hi = 0;  // set per launch from the worker count (run_plan_impl)
+  P.spec_hi = 0;  // set per launch from the worker count (worker_args)
   P.dag_prefetch = c->tun.dag_prefetch;
   P.dag_width = c->tun.dag_width;
   P.urgent_hops = c->tun.urgent_hops;
@@ -142,29 +169,7 @@ static PlanArgs plan_args(tsw_ctx* c, uint32_t n, uint32_t m, uint32_t mode, boo
   P.pred = nullptr;
   // diagnostics only: prediction hits
   if (P.dbg && n && mode == MODE_MAPD) P.pred = per_agent(c, c->d_pred, n, 0xFF);
-  // LDS residency, in priority order: agents, occupancy grid, task table
-  const size_t budget = (size_t)std::max(c->max_lds - 2048, 0);
-  bool ag = plan_lds_bytes(n, P.ncell, m, true, false, false) <= budget;
-  // without the whole set, single agent arrays in priority order (PART_*: the rules phase's serial
-  // successor walks and firing scans read SUCC / ONC / V / G; wh10k rules 3.9 -> ? s), then the rules
-  // relabel's pointer-doubling buffers
-  uint32_t part = 0;
-  if (!ag)
-    for (uint32_t bit : {PART_SUCC, PART_ONC, PART_V, PART_G, PART_NHC, PART_CANDC, PART_GT})
-      if ((c->tun.part_lds & bit) && plan_lds_bytes(n, P.ncell, m, false, false, false, false, true, part | bit) <= budget)
-        part |= bit;
-  bool fl = !ag && c->tun.flinks_lds && plan_lds_bytes(n, P.ncell, m, false, false, false, true, true, part) <= budget;
-  // the occupancy grid with the movement rounds' MU words, else OCC alone (every rules round reads
-  // OCC: C3's 170x84 fits OCC but not MU beside the agent arrays)
-  bool mu = n < 65535u && plan_lds_bytes(n, P.ncell, m, ag, true, false, fl, true, part) <= budget;  // MU32: 16-bit agent ids
-  bool oc = mu || (c->tun.occ_split && plan_lds_bytes(n, P.ncell, m, ag, true, false, fl, false, part) <= budget);
-  const bool tk = false;  // K4 reads its spatial index from global memory (the chunks it needs only)
-  P.part_lds = part;
-  P.f_lds = fl;
-  P.mu_lds = mu;
-  P.agents_lds = ag;
-  P.occ_lds = oc;
-  P.tasks_lds = tk;
+  choose_plan_lds(c, &P);
   // coop mode: lazy next hops only (eager tables have nothing left to resolve)
   P.coop = (c->tun.coop && !c->resolver && P.prefetch && c->d_cc && c->d_QS) ? 1u : 0u;
   P.hflags = c->h_flags.dev;  // watchdog words, both modes
@@ -191,18 +196,17 @@ static int build_occ(tsw_ctx* c, uint32_t n) {
   return TSW_OK;
 }
 
-// Drive k_plan until it reports done; each NEED_QUERIES exit runs K3 on the queued pairs.
 // ---- host A* service ------------------------------------------------------------------------
 // The request ring's next entry, if the planner has written it: claim it (the claim count is the tail
-// the planner reads, h_flags[3]), run the exact A* on this core and write seq << 8 | code into the reply
+// the planner reads, HF_HOST_TAIL), run the exact A* on this core and write seq << 8 | code into the reply
 // slot. Entries are claimed in ticket order by whichever serving thread sees them first. false: nothing
 // to serve. A pair the host cannot answer gets no reply: a K3 worker answers it as before.
 static bool host_serve_one(tsw_ctx* c, HostAstar& S) {
   const uint32_t mask = c->hring - 1u;
-  uint32_t t = __atomic_load_n(&c->h_flags[3], __ATOMIC_RELAXED);
+  uint32_t t = __atomic_load_n(&c->h_flags[HF_HOST_TAIL], __ATOMIC_RELAXED);
   const unsigned long long e = __atomic_load_n(&c->h_hreq[t & mask], __ATOMIC_ACQUIRE);
   if ((uint32_t)(e >> 40) != t + 1u) return false;
-  if (!__atomic_compare_exchange_n(&c->h_flags[3], &t, t + 1u, false, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED)) return true;
+  if (!__atomic_compare_exchange_n(&c->h_flags[HF_HOST_TAIL], &t, t + 1u, false, __ATOMIC_ACQ_REL, __ATOMIC_RELAXED)) return true;
   const uint32_t v = (uint32_t)(e >> 20) & 0xFFFFFu, g = (uint32_t)e & 0xFFFFFu;
   if (v >= c->G.ncell || g >= c->G.ncell || !(c->h_nbmask[v] & NB_FREE) || !(c->h_nbmask[g] & NB_FREE)) return true;
   const auto t0 = std::chrono::steady_clock::now();
@@ -253,307 +257,384 @@ static void host_service_end(tsw_ctx* c) {
   while (hp.running.load(std::memory_order_acquire) > 0) std::this_thread::yield();
 }
 
-static int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
-  *c->h_ctl = init;
-  HIPCHK(hipMemcpyAsync(c->d_ctl, c->h_ctl, sizeof(PlanCtl), hipMemcpyHostToDevice, c->s));
-  size_t lds = plan_lds_bytes(P.n, P.ncell, P.m, P.agents_lds, P.occ_lds, P.tasks_lds, P.f_lds, P.mu_lds, P.part_lds);
+// ---- the plan dispatch -------------------------------------------------------------------------
+// What one k_plan launch needs beside PlanArgs. Rebuilt when a call falls back from coop to exit mode.
+struct Dispatch {
+  size_t lds = 0;      // the planner block's dynamic LDS
+  uint32_t block = 0;  // its threads
+  WorkerArgs W{};      // coop mode: the K3 workers of workgroups 1..wblocks
+  uint32_t wblocks = 0;
+  bool serve = false;  // host A* service on
+};
+
+// Coop mode: the K3 workers' arguments and their count for a planner block of `block` threads and `lds` bytes.
+// Sets P.spec_hi; clears P.coop (exit mode) when nothing fits beside the planner.
+static int worker_args(tsw_ctx* c, PlanArgs& P, size_t lds, uint32_t block, WorkerArgs* Wp, uint32_t* wblocks) {
+  WorkerArgs& W = *Wp;
+  W.G = c->G;
+  W.cc = c->d_cc;
+  W.QN = c->d_Q;
+  W.QS = c->d_QS;
+  W.QT = c->d_QT;
+  W.QH = c->d_QH;
+  W.QP = P.QP;
+  W.klive = c->d_live;
+  W.klt = c->d_klt;
+  W.kbox = c->d_kbox;
+  W.kcnt = c->d_kcnt;
+  W.kchunks = c->kchunks;
+  W.pick = c->d_pick;
+  W.dlv = c->d_dlv;
+  W.goal_tab = c->d_goal_tab;
+  W.pred = P.pred;
+  W.nh = c->d_nh;
+  W.nstride = c->tstride;
+  // every worker may walk task chains: a chain worker serves queued needed / speculative pairs
+  // between hops (W.preempt), so chains only use otherwise idle time. Round 4 A/B (chain share 1/4
+  // -> all, profiles/r4/chain_share_ab.txt): wh10k 11.58 -> 10.25 s, C5 3.33 -> 2.76 s, C3 unchanged
+  // (it was a quarter with many agents, a half otherwise)
+  W.tmask = c->tun.chain_mask >= 0 ? (uint32_t)c->tun.chain_mask : 0u;
+  W.preempt = c->tun.chain_preempt ? 1u : 0u;
+  W.chain_hops = c->tun.chain_hops;
+  W.avoid_xcc = c->tun.avoid_xcc ? 1u : 0u;
+  W.hflags = c->h_flags.dev;
+  const WorkerCfg wcfg =
+      worker_config(c->G, c->num_cu, P.n, c->tun.wave_hcap, c->tun.worker_gs, c->tun.dag_exit, lds, c->tun.worker_fb);
+  W.dag = wcfg.dag;
+  // the test's heap scan gathers D from LDS (detour bytes) or from the u16 table in global memory:
+  // every 16 / 64 pops (C3 worker busy -20 %, wh10k 400 steps 5.77 -> 5.42 s; profiles/r3/dag_exit_ab.txt)
+  W.dag_mask = c->tun.dag_mask ? c->tun.dag_mask : (W.dag == 1u ? 15u : 63u);
+  W.stale_steps = c->tun.stale_steps;
+  W.reg_heap = c->tun.reg_heap;
+  W.wake_gate = (1u << c->tun.wake_gate) - 1u;
+  W.slow_mask = (1u << c->tun.slow_poll) - 1u;
+  W.slow_mult = c->tun.slow_mult;
+  W.idle_ticks = c->tun.worker_idle_us * 100ull;  // wall clock: 100 MHz
+  W.dt = c->d_dt;
+  W.gs_lds = wcfg.gs_lds;
+  W.stage_fb = wcfg.stage_fb;
+  W.hcap = wcfg.hcap;
+  // one dispatch: the planner (workgroup 0) and one worker workgroup on every other CU, each holding
+  // as many single-wave workers as its dynamic LDS (the planner's, whole-CU size) carves
+  W.lds_per_wave = (uint32_t)((wcfg.lds + 15u) & ~(size_t)15u);
+  W.wpb = W.lds_per_wave ? (uint32_t)std::min<size_t>(block / 64u, lds / W.lds_per_wave) : 0u;
+  const uint32_t want = W.wpb * (uint32_t)std::max(c->num_cu - 1, 0);
+  TRY(ensure_astar_scratch(c, want));  // one g-score / heap slot per worker wave
+  W.gs_all = c->d_gs;
+  W.epochs = c->d_epochs;
+  W.heaps = c->d_heaps;
+  W.ghcap = c->hcap;
+  W.nworkers = std::min(want, c->nslots);
+  P.spec_hi = 2u * W.nworkers;  // a backlog of two pairs per worker counts as keeping up
+  *wblocks = W.wpb ? (W.nworkers + W.wpb - 1u) / W.wpb : 0u;
+  if (c->tun.plan_debug)
+    fprintf(stderr, "[k_plan] workers: %u waves (%u per workgroup), g-scores %u, heap %u entries, DAG exit %u, %u B LDS each\n",
+            W.nworkers, W.wpb, wcfg.gs_lds, wcfg.hcap, wcfg.dag, W.lds_per_wave);
+  if (W.nworkers == 0 || wcfg.hcap < 4u) P.coop = 0;  // nothing fits beside the planner: exit mode
+  return TSW_OK;
+}
+
+// host A* service: coop mode only (exit mode has no waits to shorten)
+static bool host_serves(const tsw_ctx* c, const PlanArgs& P) {
+  return P.coop && c->host_threads && c->h_hreq && c->h_hrep;
+}
+
+static int host_service_args(tsw_ctx* c, PlanArgs* P) {
+  const bool serve = host_serves(c, *P);
+  P->hreq = serve ? c->h_hreq.dev : nullptr;
+  P->hrep = serve ? c->h_hrep.dev : nullptr;
+  P->hring = serve ? c->hring : 0u;
+  P->hask = nullptr;
+  P->hearly = serve ? c->tun.host_early : 0u;
+  if (P->hearly && P->n) {
+    if (c->d_hask.cap < 2 * (size_t)P->n) {
+      HIPCHK(hipStreamSynchronize(c->s));
+      HIPCHK(c->d_hask.alloc(2 * (size_t)P->n));
+    }
+    P->hask = c->d_hask;
+  }
+  return TSW_OK;
+}
+
+// Everything of a dispatch that depends on P.coop: the launch geometry, the workers, the service.
+static int setup_dispatch(tsw_ctx* c, PlanArgs& P, Dispatch* D) {
+  *D = Dispatch{};
+  const size_t planner = plan_lds_bytes(P.n, P.ncell, P.m, P.agents_lds, P.occ_lds, P.tasks_lds, P.f_lds, P.mu_lds, P.part_lds);
   // coop mode: the planner block reserves its CU's whole LDS so no worker wave is placed beside it
   // (they would compete for its SIMDs and LDS bandwidth on the critical path)
-  if (P.coop) lds = std::max<size_t>(lds, (size_t)std::max(c->max_lds - 2048, 0));
+  D->lds = P.coop ? std::max<size_t>(planner, (size_t)std::max(c->max_lds - 2048, 0)) : planner;
   // one lane per agent in the parallel passes when possible; >= 4 waves for the task argmin
-  uint32_t block = std::min<uint32_t>(PLAN_BLOCK_MAX, std::max<uint32_t>(256, (P.n + 63) / 64 * 64));
-  if (c->tun.plan_block) block = std::max<uint32_t>(64u, c->tun.plan_block);
-  WorkerArgs W{};
-  uint32_t wblocks = 0;
-  if (P.coop) {
-    W.G = c->G;
-    W.cc = c->d_cc;
-    W.QN = c->d_Q;
-    W.QS = c->d_QS;
-    W.QT = c->d_QT;
-    W.QH = c->d_QH;
-    W.QP = P.QP;
-    W.klive = c->d_live;
-    W.klt = c->d_klt;
-    W.kbox = c->d_kbox;
-    W.kcnt = c->d_kcnt;
-    W.kchunks = c->kchunks;
-    W.pick = c->d_pick;
-    W.dlv = c->d_dlv;
-    W.goal_tab = c->d_goal_tab;
-    W.pred = P.pred;
-    W.nh = c->d_nh;
-    W.nstride = c->tstride;
-    // every worker may walk task chains: a chain worker serves queued needed / speculative pairs
-    // between hops (W.preempt), so chains only use otherwise idle time. Round 4 A/B (chain share 1/4
-    // -> all, profiles/r4/chain_share_ab.txt): wh10k 11.58 -> 10.25 s, C5 3.33 -> 2.76 s, C3 unchanged
-    // (it was a quarter with many agents, a half otherwise)
-    W.tmask = c->tun.chain_mask >= 0 ? (uint32_t)c->tun.chain_mask : 0u;
-    W.preempt = c->tun.chain_preempt ? 1u : 0u;
-    W.chain_hops = c->tun.chain_hops;
-    W.avoid_xcc = c->tun.avoid_xcc ? 1u : 0u;
-    W.hflags = c->h_flags.dev;
-    const WorkerCfg wcfg =
-        worker_config(c->G, c->num_cu, P.n, c->tun.wave_hcap, c->tun.worker_gs, c->tun.dag_exit, lds, c->tun.worker_fb);
-    W.dag = wcfg.dag;
-    // the test's heap scan gathers D from LDS (detour bytes) or from the u16 table in global memory:
-    // every 16 / 64 pops (C3 worker busy -20 %, wh10k 400 steps 5.77 -> 5.42 s; profiles/r3/dag_exit_ab.txt)
-    W.dag_mask = c->tun.dag_mask ? c->tun.dag_mask : (W.dag == 1u ? 15u : 63u);
-    W.stale_steps = c->tun.stale_steps;
-    W.reg_heap = c->tun.reg_heap;
-    W.wake_gate = (1u << c->tun.wake_gate) - 1u;
-    W.slow_mask = (1u << c->tun.slow_poll) - 1u;
-    W.slow_mult = c->tun.slow_mult;
-    W.idle_ticks = c->tun.worker_idle_us * 100ull;  // wall clock: 100 MHz
-    W.dt = c->d_dt;
-    W.gs_lds = wcfg.gs_lds;
-    W.stage_fb = wcfg.stage_fb;
-    W.hcap = wcfg.hcap;
-    // one dispatch: the planner (workgroup 0) and one worker workgroup on every other CU, each holding
-    // as many single-wave workers as its dynamic LDS (the planner's, whole-CU size) carves
-    W.lds_per_wave = (uint32_t)((wcfg.lds + 15u) & ~(size_t)15u);
-    W.wpb = W.lds_per_wave ? (uint32_t)std::min<size_t>(block / 64u, lds / W.lds_per_wave) : 0u;
-    const uint32_t want = W.wpb * (uint32_t)std::max(c->num_cu - 1, 0);
-    TRY(ensure_astar_scratch(c, want));  // one g-score / heap slot per worker wave
-    W.gs_all = c->d_gs;
-    W.epochs = c->d_epochs;
-    W.heaps = c->d_heaps;
-    W.ghcap = c->hcap;
-    W.nworkers = std::min(want, c->nslots);
-    P.spec_hi = 2u * W.nworkers;  // a backlog of two pairs per worker counts as keeping up
-    wblocks = W.wpb ? (W.nworkers + W.wpb - 1u) / W.wpb : 0u;
-    if (c->tun.plan_debug)
-      fprintf(stderr, "[k_plan] workers: %u waves (%u per workgroup), g-scores %u, heap %u entries, DAG exit %u, %u B LDS each\n",
-              W.nworkers, W.wpb, wcfg.gs_lds, wcfg.hcap, wcfg.dag, W.lds_per_wave);
-    if (W.nworkers == 0 || wcfg.hcap < 4u) P.coop = 0;  // nothing fits beside the planner: exit mode
-  }
-  // host A* service: coop mode only (exit mode has no waits to shorten)
-  const bool serve = P.coop && c->host_threads && c->h_hreq && c->h_hrep;
-  P.hreq = serve ? c->h_hreq.dev : nullptr;
-  P.hrep = serve ? c->h_hrep.dev : nullptr;
-  P.hring = serve ? c->hring : 0u;
-  P.hask = nullptr;
-  P.hearly = serve ? c->tun.host_early : 0u;
-  if (P.hearly && P.n) {
-    if (c->d_hask.cap < 2 * (size_t)P.n) {
-      HIPCHK(hipStreamSynchronize(c->s));
-      HIPCHK(c->d_hask.alloc(2 * (size_t)P.n));
-    }
-    P.hask = c->d_hask;
-  }
+  D->block = std::min<uint32_t>(PLAN_BLOCK_MAX, std::max<uint32_t>(256, (P.n + 63) / 64 * 64));
+  if (c->tun.plan_block) D->block = std::max<uint32_t>(64u, c->tun.plan_block);
+  if (P.coop) TRY(worker_args(c, P, D->lds, D->block, &D->W, &D->wblocks));
+  TRY(host_service_args(c, &P));
+  D->serve = host_serves(c, P);
   if (c->tun.plan_debug)
     fprintf(stderr, "[k_plan] planner LDS: agents %u part 0x%x flinks %u occ %u mu %u tasks %u (%zu B)\n", P.agents_lds,
-            P.part_lds, P.f_lds, P.occ_lds, P.mu_lds, P.tasks_lds,
-            plan_lds_bytes(P.n, P.ncell, P.m, P.agents_lds, P.occ_lds, P.tasks_lds, P.f_lds, P.mu_lds, P.part_lds));
-  const bool coop = P.coop != 0;
-  // every return below happens after the dispatch has drained (workers included): nothing of this
-  // call keeps running into the next one
-  for (uint64_t round = 0;; ++round) {
-    if (round > 16ull * P.n + 4096ull * (init.max_t + 1)) RET(TSW_EINVAL, "plan kernel made no progress");
-    if (coop) {
-      HIPCHK(hipMemsetAsync(c->d_cc, 0, sizeof(CoopCtl), c->s));
-      // tickets restart at 0 with every launch: no request word of an earlier one may match
-      if (P.hask) HIPCHK(hipMemsetAsync(c->d_hask, 0, (size_t)P.n * 2u * sizeof(unsigned long long), c->s));
-      const uint32_t nt = P.mode == MODE_MAPD ? c->qt_count : 0u;
-      if (nt) HIPCHK(hipMemcpyAsync(&c->d_cc->head_t, &c->qt_count, 4, hipMemcpyHostToDevice, c->s));
-    }
-    {
-      volatile uint32_t* hf = c->h_flags;
-      hf[0] = 0u;
-      hf[1] = 0u;
-      hf[2] = 0u;
-      for (int w = 3; w < 40; ++w) hf[w] = 0u;  // host A* tail [3], barrier breadcrumbs (TSW_PLAN_DEBUG)
-      if (serve) {
-        memset(c->h_hreq, 0, (size_t)c->hring * sizeof(unsigned long long));
-        memset(c->h_hrep, 0, (size_t)c->hring * sizeof(uint32_t));
+            P.part_lds, P.f_lds, P.occ_lds, P.mu_lds, P.tasks_lds, planner);
+  return TSW_OK;
+}
+
+static int upload_ctl(tsw_ctx* c, const PlanCtl& ctl) {
+  *c->h_ctl = ctl;
+  HIPCHK(hipMemcpyAsync(c->d_ctl, c->h_ctl, sizeof(PlanCtl), hipMemcpyHostToDevice, c->s));
+  return TSW_OK;
+}
+
+// What the planner, the workers and the host share is zeroed before every launch.
+static int reset_dispatch(tsw_ctx* c, const PlanArgs& P, bool serve) {
+  if (P.coop) {
+    HIPCHK(hipMemsetAsync(c->d_cc, 0, sizeof(CoopCtl), c->s));
+    // tickets restart at 0 with every launch: no request word of an earlier one may match
+    if (P.hask) HIPCHK(hipMemsetAsync(c->d_hask, 0, (size_t)P.n * 2u * sizeof(unsigned long long), c->s));
+    const uint32_t nt = P.mode == MODE_MAPD ? c->qt_count : 0u;
+    if (nt) HIPCHK(hipMemcpyAsync(&c->d_cc->head_t, &c->qt_count, 4, hipMemcpyHostToDevice, c->s));
+  }
+  volatile uint32_t* hf = c->h_flags;
+  for (int w = 0; w < HF_WORDS; ++w) hf[w] = 0u;
+  if (serve) {
+    memset(c->h_hreq, 0, (size_t)c->hring * sizeof(unsigned long long));
+    memset(c->h_hrep, 0, (size_t)c->hring * sizeof(uint32_t));
+  }
+  return TSW_OK;
+}
+
+// The helper pool serves for the lifetime of this object: every exit from the wait parks the helpers again.
+struct HostServiceScope {
+  tsw_ctx* c;
+  HostServiceScope(tsw_ctx* c_, bool serve) : c(serve ? c_ : nullptr) {
+    if (c) host_service_begin(c);
+  }
+  ~HostServiceScope() {
+    if (c) host_service_end(c);
+  }
+  HostServiceScope(const HostServiceScope&) = delete;
+  HostServiceScope& operator=(const HostServiceScope&) = delete;
+};
+
+// The watchdog (PlanWatchdog, tsw_plan.h) said so: raise the abort word. In coop mode the planner's waits
+// give up (it exits to the host), the workers leave and the rest of the call runs in exit mode; a planner
+// stuck anywhere else sees the word in its round loops and exits with ERR_ABORT and its position. A fault
+// can then cost time or fail the call, but never hang it.
+static void raise_abort(tsw_ctx* c, volatile uint32_t* hf) {
+  hf[HF_ABORT] = 1u;
+  ++c->coop_aborts;
+  ++c->st.watchdog_fires;
+  if (c->watchdog_ms >= 1000u)
+    fprintf(stderr, "[tswap] watchdog: planner made no step for %u ms; finishing the call in exit mode\n", c->watchdog_ms);
+  if (c->tun.plan_debug && hf[HF_BAR_COUNT]) {  // per-wave barrier breadcrumbs (-DTSW_PBAR): line | 0x10000 once passed
+    fprintf(stderr, "[tswap] planner waves at barriers:");
+    for (int w = 0; w < PLAN_WAVES_MAX; ++w)
+      fprintf(stderr, " %u%s", hf[HF_BAR_LINE + w] & 0xFFFFu, (hf[HF_BAR_LINE + w] >> 16) ? "+" : "");
+    fprintf(stderr, "\n[tswap] barriers passed per wave:");
+    for (int w = 0; w < PLAN_WAVES_MAX; ++w) fprintf(stderr, " %u", hf[HF_BAR_COUNT + w]);
+    fprintf(stderr, "\n[tswap] first mismatch: wave 0 at %u, another at %u\n", hf[HF_BAR_MISMATCH] >> 16,
+            hf[HF_BAR_MISMATCH] & 0xFFFFu);
+  }
+}
+
+// Wait for the launched dispatch: poll the stream and the planner's heartbeat every 50 us. With the host A*
+// service on, this thread serves the request ring between the checks, which then run on a 50 us time basis
+// instead of after a 50 us sleep. The first check comes at once.
+static int wait_dispatch(tsw_ctx* c, bool serve) {
+  using Clock = PlanWatchdog::Clock;
+  volatile uint32_t* hf = c->h_flags;
+  auto next_check = Clock::now();
+  PlanWatchdog watchdog(c->watchdog_ms, hf[HF_HEARTBEAT], next_check);
+  HostServiceScope helpers(c, serve);
+  for (;;) {
+    if (serve) {
+      const bool any = host_serve_one(c, c->host_scratch[0]);
+      if (Clock::now() < next_check) {
+        if (!any) __builtin_ia32_pause();
+        continue;
       }
     }
+    const hipError_t q = hipStreamQuery(c->s);
+    if (q == hipSuccess) return TSW_OK;
+    if (q != hipErrorNotReady) HIPCHK(q);
+    const uint32_t hb = hf[HF_HEARTBEAT];
+    if (watchdog.check(hb, hf[HF_ABORT], Clock::now())) raise_abort(c, hf);
+    if (serve) next_check = Clock::now() + std::chrono::microseconds(50);
+    else std::this_thread::sleep_for(std::chrono::microseconds(50));
+  }
+}
+
+// Coop mode, after the dispatch has drained: the workers' and the waits' counters into the stats, the
+// workers' error word, and the speculative pairs nobody claimed.
+static int harvest_coop(tsw_ctx* c, const WorkerArgs& W) {
+  HIPCHK(hipMemcpy(c->h_cc, c->d_cc, sizeof(CoopCtl), hipMemcpyDeviceToHost));
+  const CoopCtl& cc = *c->h_cc;
+  c->st.host_astar_queries += c->host_queries.exchange(0);
+  c->st.host_astar_ms += (double)c->host_busy_ns.exchange(0) * 1e-6;
+  c->st.host_astar_used += cc.host_used;
+  c->st.coop_waits += cc.waits;
+  c->st.coop_wait_ms += (double)cc.wait_ticks / (double)c->wall_khz;
+  for (int k = 0; k < 8; ++k) {
+    c->st.coop_wait_sec_ms[k] += (double)cc.wait_sec[k] / (double)c->wall_khz;
+    c->st.coop_waits_sec[k] += cc.waits_sec[k];
+  }
+  c->st.astar_queries += cc.worker_queries;
+  c->st.coop_workers = W.nworkers;
+  for (int k = 0; k < 3; ++k) {
+    c->st.coop_worker_busy_ms[k] += (double)cc.wbusy[k] / (double)c->wall_khz;
+    c->st.coop_worker_queries[k] += cc.wcount[k];
+    c->st.coop_worker_pops[k] += cc.wpops[k];
+  }
+  if (cc.err) RET(TSW_EOVERFLOW, "K3 worker: A* heap overflow");
+  // speculative pairs nobody claimed stay PENDING_S: back to UNKNOWN for later calls — only the
+  // unclaimed queue entries (every claimed one was resolved, or reset by the worker that dropped
+  // it as stale): a whole-store sweep cost C5 ~4 s per call (18 GB of codes)
+  if (cc.head_s > cc.claim_s) {
+    HIPCHK(launch_reset_queue(c->d_QS, cc.claim_s, std::min<uint32_t>(cc.head_s, (uint32_t)c->d_QS.cap), c->d_nh,
+                              c->tstride, c->s));
+    HIPCHK(hipStreamSynchronize(c->s));
+  }
+  return TSW_OK;
+}
+
+// ---- TSW_PLAN_DEBUG report ---------------------------------------------------------------------
+static hipError_t read_ticks(tsw_ctx* c, unsigned long long (&tk)[TK_COUNT]) {
+  return hipMemcpy(tk, c->d_ticks, sizeof tk, hipMemcpyDeviceToHost);
+}
+
+// where the stopped planner spent its time: the section and sub-phase slots up to the ASSIGN ones
+static void plan_debug_stop(tsw_ctx* c) {
+  unsigned long long tk[TK_COUNT];
+  if (read_ticks(c, tk) != hipSuccess) return;
+  std::string line = "[k_plan] watchdog stop, ticks:";
+  for (int q = 0; q <= TK_ASG_SECTIONS; ++q) line += " " + std::to_string(q) + ":" + std::to_string(tk[q]);
+  fprintf(stderr, "%s\n", line.c_str());
+}
+
+static void coop_debug_report(tsw_ctx* c) {
+  const CoopCtl& cc = *c->h_cc;
+  fprintf(stderr, "[k_plan] needed pairs unresolved (never queued / queued speculatively): PRE1 %u/%u RULES %u/%u "
+          "MOVE %u/%u | PRE1 never queued: assigned %u, picked up %u | chain queries %llu of %llu | host asked %u (early %u) "
+          "used %u (early, in refresh %u)\n", cc.dbg_need[0], cc.dbg_need[1], cc.dbg_need[2],
+          cc.dbg_need[3], cc.dbg_need[4], cc.dbg_need[5], cc.dbg_need[6], cc.dbg_need[7],
+          (unsigned long long)cc.chain_queries, (unsigned long long)cc.worker_queries, cc.host_asked, cc.early_asked,
+          cc.host_used, cc.early_taken);
+  {
+    static const char* nm[6] = {"r3b", "r3s", "rot", "mv", "asg", "pick"};
+    std::string line = "[k_plan] PRE1 unresolved by agent change (unknown/pending):";
+    for (int tg = 0; tg < 64; ++tg) {
+      if (!cc.dbg_tag[0][tg] && !cc.dbg_tag[1][tg]) continue;
+      std::string name;
+      for (int b = 0; b < 6; ++b)
+        if (tg & (1 << b)) name += (name.empty() ? "" : "+") + std::string(nm[b]);
+      char buf[96];
+      snprintf(buf, sizeof buf, " %s %u/%u", name.empty() ? "none" : name.c_str(), cc.dbg_tag[0][tg], cc.dbg_tag[1][tg]);
+      line += buf;
+    }
+    fprintf(stderr, "%s\n", line.c_str());
+  }
+  fprintf(stderr, "[k_plan] speculative pairs dropped as stale: %u (older than %u timesteps)\n",
+          cc.spec_dropped, c->tun.stale_steps);
+  fprintf(stderr, "[k_plan] predicted chains: %u jobs | assignments %u: predicted task %u, no prediction %u\n",
+          cc.pred_jobs, cc.pred_asg, cc.pred_hit, cc.pred_none);
+  fprintf(stderr, "[k_plan] spec backlog at wait start: avg %.1f max %u | queue delay enqueue -> claim: needed "
+          "avg %.1f us (%u > 1 ms, %u already resolved), speculative avg %.1f timesteps (%u > 1, %u already resolved)\n",
+          cc.waits ? (double)cc.dbg_depth / cc.waits : 0.0, cc.dbg_depth_max,
+          cc.wcount[0] ? cc.qdelay[0] / 100.0 / cc.wcount[0] : 0.0, cc.qlate[0], cc.qskip[0],
+          cc.wcount[1] ? (double)cc.qdelay[1] / cc.wcount[1] : 0.0, cc.qlate[1], cc.qskip[1]);
+  fprintf(stderr, "[k_plan] worker A* ms (queries, pops): needed %.1f (%u, %llu) spec %.1f (%u, %llu) task chains "
+          "%.1f (%u, %llu) | tier-2 hand-offs %llu tier-3 %llu | detour staging %.1f ms (%u)\n",
+          cc.wbusy[0] / (double)c->wall_khz, cc.wcount[0], cc.wpops[0], cc.wbusy[1] / (double)c->wall_khz,
+          cc.wcount[1], cc.wpops[1], cc.wbusy[2] / (double)c->wall_khz, cc.wcount[2], cc.wpops[2],
+          cc.wpops[3] & 0xFFFFFFFFull, cc.wpops[3] >> 32, cc.wbusy[3] / (double)c->wall_khz, cc.wcount[3]);
+}
+
+// The finished plan's report: k_plan's tick slots (wall-clock ticks as us, shader cycles as kcycles) and,
+// in coop mode, the workers' counters of the last dispatch.
+static int plan_debug_report(tsw_ctx* c, const PlanCtl& k, uint64_t launches, bool coop) {
+  unsigned long long tk[TK_COUNT];
+  HIPCHK(read_ticks(c, tk));
+  const auto us = [&](TickSlot s) { return tk[s] / 100.0; };
+  const auto kcyc = [&](TickSlot s) { return tk[s] / 1e3; };
+  fprintf(stderr, "[k_plan] assign us: transitions %.0f compaction %.0f scan %.0f accept %.0f update %.0f | sections %llu batches %llu accepted %llu\n",
+          us(TK_ASG_TRANSITIONS), us(TK_ASG_COMPACT), us(TK_ASG_SCAN), us(TK_ASG_ACCEPT), us(TK_ASG_UPDATE),
+          tk[TK_ASG_SECTIONS], tk[TK_ASG_BATCHES], tk[TK_ASG_ACCEPTED]);
+  // the scan's parts as thread 0 sees them (the closing part includes its wait for the slowest wave)
+  fprintf(stderr, "[k_plan] assign scan us: index %.0f bound %.0f entries %.0f reduce %.0f | chunk-agent pairs %llu chunks %llu "
+          "scanning waves %llu list rounds %llu | batch widths 1: %llu 2-4: %llu 5-8: %llu 9-16: %llu\n",
+          us(TK_SCAN_INDEX), us(TK_SCAN_BOUND), us(TK_SCAN_ENTRIES), us(TK_SCAN_REDUCE), tk[TK_SCAN_PAIRS],
+          tk[TK_SCAN_CHUNKS], tk[TK_SCAN_WAVES], tk[TK_SCAN_ROUNDS], tk[TK_SCAN_B_ONE], tk[TK_SCAN_B_LE4],
+          tk[TK_SCAN_B_LE8], tk[TK_SCAN_B_MORE]);
+  // walk-ahead (round 14): steps whose walk ran in PRE1 / that PRE1 left to the rules phase / whose walk the
+  // waves beside wave 0 finished and published there (counted by the publishing wave), those walkers' time
+  // from arming to the last wave's count, steps in which wave 0 was done before them
+  fprintf(stderr, "[k_plan] PRE1 publish us %.0f (%llu) | rules init us %.0f prefetch us %.0f publish us %.0f (%llu)"
+          " | walk-ahead steps in PRE1 %llu left to RULES %llu done in RULES %llu walkers us %.0f wave 0 first %llu\n",
+          us(TK_PRE1_PUBLISH), tk[TK_PRE1_PUBLISHES], us(TK_RULES_INIT), us(TK_RULES_PREFETCH), us(TK_RULES_PUBLISH),
+          tk[TK_RULES_PUBLISHES], tk[TK_WALK_IN_PRE1], tk[TK_WALK_LEFT], tk[TK_WALK_IN_RULES], us(TK_WALKERS),
+          tk[TK_WALK_WAVE0_FIRST]);
+  fprintf(stderr, "[k_plan] wave rules kcycles: load %.0f stale %.0f fast %.0f update %.0f slow %.0f rot %.0f | "
+          "loads %llu fast firings %llu | rotations %llu, settle kcycles: successors %.0f walk %.0f\n",
+          kcyc(TK_WR_LOAD), kcyc(TK_WR_STALE), kcyc(TK_WR_FAST), kcyc(TK_WR_UPDATE), kcyc(TK_WR_SLOW), kcyc(TK_WR_ROT),
+          tk[TK_WR_LOADS], tk[TK_WR_FAST_FIRINGS], tk[TK_R4_ROTATIONS], kcyc(TK_SETTLE_SUCC), kcyc(TK_SETTLE_WALK));
+  fprintf(stderr, "[k_plan] wave rules batches %llu (longest walks %llu hops) kcycles: marks %.0f walks %.0f apply %.0f\n",
+          tk[TK_WB_BATCHES], tk[TK_WB_HOPS], kcyc(TK_WB_MARKS), kcyc(TK_WB_WALKS), kcyc(TK_WB_APPLY));
+  fprintf(stderr, "[k_plan] steps %u rule rounds %u move rounds %u launches %llu | move passes us %.0f %.0f %.0f"
+          " | rule-3 walk hops %llu rotations %llu | rules scan %.0f fire %.0f relabel %.0f\n", k.steps_run, k.rule_rounds,
+          k.move_rounds, (unsigned long long)launches, us(TK_MOVE_PASS1), us(TK_MOVE_PASS2), us(TK_MOVE_PASS3),
+          tk[TK_R3_WALK_HOPS], tk[TK_R4_ROTATIONS], us(TK_RULES_SCAN), us(TK_RULES_FIRE), us(TK_RULES_RELABEL));
+  if (coop) coop_debug_report(c);
+  return TSW_OK;
+}
+
+// PlanCtl::err as the call's return code and error string (PLAN_ERR_TABLE, tsw_plan.h); TSW_OK: no error.
+static int plan_error(tsw_ctx* c, const PlanCtl& k) {
+  const PlanErrRow* row = plan_err_row(k.err);
+  if (!row) return TSW_OK;
+  if (row->msg) RET(row->code, row->msg);
+  char buf[256];
+  if (row->bits == ERR_ABORT) {
+    if (c->tun.plan_debug) plan_debug_stop(c);
+    snprintf(buf, sizeof buf,
+             "planner stopped by the watchdog (no timestep for %u ms): t %u section %u cursor %u, %u rule rounds, "
+             "%u move rounds", c->watchdog_ms, k.t, k.section, k.i, k.rule_rounds, k.move_rounds);
+  } else {
+    snprintf(buf, sizeof buf, "plan kernel error bits 0x%x", k.err);
+  }
+  RET(row->code, buf);
+}
+
+// Drive k_plan from `init` until it reports done. Coop mode: one dispatch runs the planner and the K3 workers;
+// a planner that gave up waiting has its needed queue resolved here and is relaunched. Exit mode: each
+// NEED_QUERIES exit runs K3 on the queued pairs. After a watchdog firing a coop call goes on in exit mode.
+// Every return happens after the dispatch has drained (workers included): nothing of this call keeps
+// running into the next one.
+static int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
+  Dispatch D;
+  TRY(upload_ctl(c, init));
+  TRY(setup_dispatch(c, P, &D));
+  uint64_t bound = 16ull * P.n + 4096ull * (init.max_t + 1);  // launches without reaching the end
+  for (uint64_t launches = 0;;) {
+    if (launches > bound) RET(TSW_EINVAL, "plan kernel made no progress");
+    const bool coop = P.coop != 0;
+    TRY(reset_dispatch(c, P, D.serve));
     {
       Timer t(c, CAT_WALK);
-      HIPCHK(launch_plan(P, c->d_pargs, coop ? &W : nullptr, wblocks, lds, block, c->s));
-      c->st.plan_block = block;
+      HIPCHK(launch_plan(P, c->d_pargs, coop ? &D.W : nullptr, D.wblocks, D.lds, D.block, c->s));
+      c->st.plan_block = D.block;
     }
+    ++launches;
     c->st.walker_launches++;
     if (coop) c->st.astar_launches++;
     HIPCHK(hipMemcpyAsync(c->h_ctl, c->d_ctl, sizeof(PlanCtl), hipMemcpyDeviceToHost, c->s));
-    {
-      // watchdog: the planner publishes its timestep count; if it stops moving for 10 s while the
-      // planner still runs, raise `abort`. In coop mode its waits give up (it exits to the host),
-      // the workers leave and the rest of the call runs in exit mode; a planner stuck anywhere else
-      // sees the flag in its round loops and exits with ERR_ABORT and its position. A fault can
-      // then cost time or fail the call, but never hang it.
-      volatile uint32_t* hf = c->h_flags;
-      uint32_t last = hf[2];
-      auto seen = std::chrono::steady_clock::now();
-      // host A* service: this thread serves the request ring between the checks below, which then run
-      // on a 50 us time basis instead of after a 50 us sleep
-      auto next_check = seen;
-      if (serve) host_service_begin(c);
-      for (;;) {
-        if (serve) {
-          const bool any = host_serve_one(c, c->host_scratch[0]);
-          if (std::chrono::steady_clock::now() < next_check) {
-            if (!any) __builtin_ia32_pause();
-            continue;
-          }
-        }
-        const hipError_t q = hipStreamQuery(c->s);
-        if (q == hipSuccess) break;
-        if (q != hipErrorNotReady) {
-          if (serve) host_service_end(c);
-          HIPCHK(q);
-        }
-        const uint32_t hb = hf[2];
-        const auto now = std::chrono::steady_clock::now();
-        if (hb != last) {
-          last = hb;
-          seen = now;
-        } else if (!hf[1] && now - seen > std::chrono::milliseconds(c->watchdog_ms)) {
-          hf[1] = 1u;
-          ++c->coop_aborts;
-          ++c->st.watchdog_fires;
-          if (c->watchdog_ms >= 1000u)
-            fprintf(stderr, "[tswap] watchdog: planner made no step for %u ms; finishing the call in exit mode\n",
-                    c->watchdog_ms);
-          if (c->tun.plan_debug && hf[24]) {  // per-wave barrier breadcrumbs (-DTSW_PBAR): line | 0x10000 once passed
-            fprintf(stderr, "[tswap] planner waves at barriers:");
-            for (int w = 0; w < 16; ++w) fprintf(stderr, " %u%s", hf[8 + w] & 0xFFFFu, (hf[8 + w] >> 16) ? "+" : "");
-            fprintf(stderr, "\n[tswap] barriers passed per wave:");
-            for (int w = 0; w < 16; ++w) fprintf(stderr, " %u", hf[24 + w]);
-            fprintf(stderr, "\n[tswap] first mismatch: wave 0 at %u, another at %u\n", hf[4] >> 16, hf[4] & 0xFFFFu);
-          }
-        }
-        if (serve) next_check = std::chrono::steady_clock::now() + std::chrono::microseconds(50);
-        else std::this_thread::sleep_for(std::chrono::microseconds(50));
-      }
-      if (serve) host_service_end(c);
-    }
+    TRY(wait_dispatch(c, D.serve));
     HIPCHK(hipStreamSynchronize(c->s));
-    if (coop) {
-      HIPCHK(hipMemcpy(c->h_cc, c->d_cc, sizeof(CoopCtl), hipMemcpyDeviceToHost));
-      const CoopCtl& cc = *c->h_cc;
-      c->st.host_astar_queries += c->host_queries.exchange(0);
-      c->st.host_astar_ms += (double)c->host_busy_ns.exchange(0) * 1e-6;
-      c->st.host_astar_used += cc.host_used;
-      c->st.coop_waits += cc.waits;
-      c->st.coop_wait_ms += (double)cc.wait_ticks / (double)c->wall_khz;
-      for (int k = 0; k < 8; ++k) {
-        c->st.coop_wait_sec_ms[k] += (double)cc.wait_sec[k] / (double)c->wall_khz;
-        c->st.coop_waits_sec[k] += cc.waits_sec[k];
-      }
-      c->st.astar_queries += cc.worker_queries;
-      c->st.coop_workers = W.nworkers;
-      for (int k = 0; k < 3; ++k) {
-        c->st.coop_worker_busy_ms[k] += (double)cc.wbusy[k] / (double)c->wall_khz;
-        c->st.coop_worker_queries[k] += cc.wcount[k];
-        c->st.coop_worker_pops[k] += cc.wpops[k];
-      }
-      if (cc.err) RET(TSW_EOVERFLOW, "K3 worker: A* heap overflow");
-      // speculative pairs nobody claimed stay PENDING_S: back to UNKNOWN for later calls — only the
-      // unclaimed queue entries (every claimed one was resolved, or reset by the worker that dropped
-      // it as stale): a whole-store sweep cost C5 ~4 s per call (18 GB of codes)
-      if (cc.head_s > cc.claim_s) {
-        HIPCHK(launch_reset_queue(c->d_QS, cc.claim_s, std::min<uint32_t>(cc.head_s, (uint32_t)c->d_QS.cap), c->d_nh,
-                                  c->tstride, c->s));
-        HIPCHK(hipStreamSynchronize(c->s));
-      }
-    }
-    const PlanCtl& k = *c->h_ctl;
-    if (k.err & ERR_ABORT) {
-      if (c->tun.plan_debug) {  // diagnostics: where the stopped planner spent its time (section / sub-phase ticks)
-        unsigned long long tk[48];
-        if (hipMemcpy(tk, c->d_ticks, sizeof tk, hipMemcpyDeviceToHost) == hipSuccess) {
-          std::string line = "[k_plan] watchdog stop, ticks:";
-          for (int q = 0; q < 40; ++q) line += " " + std::to_string(q) + ":" + std::to_string(tk[q]);
-          fprintf(stderr, "%s\n", line.c_str());
-        }
-      }
-      char buf[256];
-      snprintf(buf, sizeof buf,
-               "planner stopped by the watchdog (no timestep for %u ms): t %u section %u cursor %u, %u rule rounds, "
-               "%u move rounds", c->watchdog_ms, k.t, k.section, k.i, k.rule_rounds, k.move_rounds);
-      RET(TSW_EINVAL, buf);
-    }
-    if (k.err & ERR_BAD_PICKUP)
-      RET(TSW_EINVAL, "assigned task's pickup is off-grid or blocked (reference panics at tswap.rs:136)");
-    if (k.err & ERR_BAD_DELIVERY)
-      RET(TSW_EINVAL, "reached pickup's task delivery is off-grid or blocked (reference panics at tswap.rs:112)");
-    if (k.err) {
-      char buf[128];
-      snprintf(buf, sizeof buf, "plan kernel error bits 0x%x", k.err);
-      RET((k.err & ERR_NO_TABLE) ? TSW_EINVAL : TSW_EOVERFLOW, buf);
-    }
+    if (coop) TRY(harvest_coop(c, D.W));
+    const PlanCtl k = *c->h_ctl;
+    TRY(plan_error(c, k));
     c->st.relabels_full += k.relabel_full;
     c->st.relabels_inc += k.relabel_inc;
     if (k.status == PLAN_DONE) {
       c->chase_id = k.chase_id;
       c->st.rule_rounds += k.rule_rounds;
       c->st.move_rounds += k.move_rounds;
-      if (c->tun.plan_debug) {
-        unsigned long long tk[64];
-        HIPCHK(hipMemcpy(tk, c->d_ticks, sizeof tk, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[k_plan] assign us: transitions %.0f compaction %.0f scan %.0f accept %.0f update %.0f | sections %llu batches %llu accepted %llu\n",
-                tk[32] / 100.0, tk[33] / 100.0, tk[34] / 100.0, tk[35] / 100.0, tk[36] / 100.0, tk[39], tk[37], tk[38]);
-        // the scan's parts as thread 0 sees them (the closing part includes its wait for the slowest wave)
-        fprintf(stderr, "[k_plan] assign scan us: index %.0f bound %.0f entries %.0f reduce %.0f | chunk-agent pairs %llu chunks %llu "
-                "scanning waves %llu list rounds %llu | batch widths 1: %llu 2-4: %llu 5-8: %llu 9-16: %llu\n",
-                tk[48] / 100.0, tk[49] / 100.0, tk[50] / 100.0, tk[51] / 100.0, tk[52], tk[53], tk[54], tk[60], tk[55], tk[56],
-                tk[57], tk[58]);
-        // walk-ahead (round 14): steps whose walk ran in PRE1 / that PRE1 left to the rules phase / whose walk the
-        // waves beside wave 0 finished and published there (counted by the publishing wave), those walkers' time
-        // from arming to the last wave's count, steps in which wave 0 was done before them
-        fprintf(stderr, "[k_plan] PRE1 publish us %.0f (%llu) | rules init us %.0f prefetch us %.0f publish us %.0f (%llu)"
-                " | walk-ahead steps in PRE1 %llu left to RULES %llu done in RULES %llu walkers us %.0f wave 0 first %llu\n",
-                tk[24] / 100.0, tk[25], tk[26] / 100.0, tk[27] / 100.0, tk[28] / 100.0, tk[29], tk[45], tk[46], tk[62],
-                tk[61] / 100.0, tk[47]);
-        fprintf(stderr, "[k_plan] wave rules kcycles: load %.0f stale %.0f fast %.0f update %.0f slow %.0f rot %.0f | "
-                "loads %llu fast firings %llu | rotations %llu, settle kcycles: successors %.0f walk %.0f\n",
-                tk[16] / 1e3, tk[17] / 1e3, tk[18] / 1e3, tk[19] / 1e3, tk[20] / 1e3, tk[21] / 1e3, tk[22], tk[23],
-                tk[11], tk[30] / 1e3, tk[31] / 1e3);
-        fprintf(stderr, "[k_plan] wave rules batches %llu (longest walks %llu hops) kcycles: marks %.0f walks %.0f apply %.0f\n",
-                tk[43], tk[44], tk[40] / 1e3, tk[41] / 1e3, tk[42] / 1e3);
-        fprintf(stderr, "[k_plan] steps %u rule rounds %u move rounds %u launches %llu | move A-E us %.0f %.0f %.0f %.0f %.0f"
-                " | rules scan %.0f fire %.0f relabel %.0f\n", k.steps_run, k.rule_rounds, k.move_rounds,
-                (unsigned long long)round + 1ull, tk[8] / 100.0, tk[9] / 100.0, tk[10] / 100.0, tk[11] / 100.0,
-                tk[12] / 100.0, tk[13] / 100.0, tk[14] / 100.0, tk[15] / 100.0);
-        if (coop) {
-          const CoopCtl& cc = *c->h_cc;
-          fprintf(stderr, "[k_plan] needed pairs unresolved (never queued / queued speculatively): PRE1 %u/%u RULES %u/%u "
-                  "MOVE %u/%u | PRE1 never queued: assigned %u, picked up %u | chain queries %llu of %llu | host asked %u (early %u) "
-                  "used %u (early, in refresh %u)\n", cc.dbg_need[0], cc.dbg_need[1], cc.dbg_need[2],
-                  cc.dbg_need[3], cc.dbg_need[4], cc.dbg_need[5], cc.dbg_need[6], cc.dbg_need[7],
-                  (unsigned long long)cc.chain_queries, (unsigned long long)cc.worker_queries, cc.host_asked, cc.early_asked,
-                  cc.host_used, cc.early_taken);
-          {
-            static const char* nm[6] = {"r3b", "r3s", "rot", "mv", "asg", "pick"};
-            std::string line = "[k_plan] PRE1 unresolved by agent change (unknown/pending):";
-            for (int tg = 0; tg < 64; ++tg) {
-              if (!cc.dbg_tag[0][tg] && !cc.dbg_tag[1][tg]) continue;
-              std::string name;
-              for (int b = 0; b < 6; ++b)
-                if (tg & (1 << b)) name += (name.empty() ? "" : "+") + std::string(nm[b]);
-              char buf[96];
-              snprintf(buf, sizeof buf, " %s %u/%u", name.empty() ? "none" : name.c_str(), cc.dbg_tag[0][tg], cc.dbg_tag[1][tg]);
-              line += buf;
-            }
-            fprintf(stderr, "%s\n", line.c_str());
-          }
-          fprintf(stderr, "[k_plan] speculative pairs dropped as stale: %u (older than %u timesteps)\n",
-                  cc.spec_dropped, c->tun.stale_steps);
-          fprintf(stderr, "[k_plan] predicted chains: %u jobs | assignments %u: predicted task %u, no prediction %u\n",
-                  cc.pred_jobs, cc.pred_asg, cc.pred_hit, cc.pred_none);
-          fprintf(stderr, "[k_plan] spec backlog at wait start: avg %.1f max %u | queue delay enqueue -> claim: needed "
-                  "avg %.1f us (%u > 1 ms, %u already resolved), speculative avg %.1f timesteps (%u > 1, %u already resolved)\n",
-                  cc.waits ? (double)cc.dbg_depth / cc.waits : 0.0, cc.dbg_depth_max,
-                  cc.wcount[0] ? cc.qdelay[0] / 100.0 / cc.wcount[0] : 0.0, cc.qlate[0], cc.qskip[0],
-                  cc.wcount[1] ? (double)cc.qdelay[1] / cc.wcount[1] : 0.0, cc.qlate[1], cc.qskip[1]);
-          fprintf(stderr, "[k_plan] worker A* ms (queries, pops): needed %.1f (%u, %llu) spec %.1f (%u, %llu) task chains "
-                  "%.1f (%u, %llu) | tier-2 hand-offs %llu tier-3 %llu | detour staging %.1f ms (%u)\n",
-                  cc.wbusy[0] / (double)c->wall_khz, cc.wcount[0], cc.wpops[0], cc.wbusy[1] / (double)c->wall_khz,
-                  cc.wcount[1], cc.wpops[1], cc.wbusy[2] / (double)c->wall_khz, cc.wcount[2], cc.wpops[2],
-                  cc.wpops[3] & 0xFFFFFFFFull, cc.wpops[3] >> 32, cc.wbusy[3] / (double)c->wall_khz, cc.wcount[3]);
-        }
-      }
+      if (c->tun.plan_debug) TRY(plan_debug_report(c, k, launches, coop));
       // exit mode: pairs the prefetch queued but no firing needed — resolve them so no table entry
       // is left PENDING for later calls (coop mode: the workers drained the needed queue)
       if (!coop && k.qcount > 0) {
@@ -563,32 +644,36 @@ static int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
       return TSW_OK;
     }
     c->st.plan_exits[std::min<uint32_t>(k.section, 7u)]++;
-    if (coop) {
-      if (k.status != PLAN_NEED_QUERIES) RET(TSW_EINVAL, "plan kernel stopped without resolvable next hops");
-      if (c->h_flags[1]) {
-        // watchdog fired: finish this call in exit mode (host-side K3 passes at planner exits);
-        // pairs the aborted workers left queued are unqueued first
-        HIPCHK(launch_reset_pending(c->d_nh, (uint64_t)c->tab_count * c->tstride, c->s));
-        HIPCHK(hipStreamSynchronize(c->s));
-        P.coop = 0;
-        PlanCtl resume = k;
-        resume.status = PLAN_RUNNING;
-        resume.qcount = 0;
-        return run_plan_impl(c, P, resume);
-      }
-      // the planner gave up waiting (no worker left — they exit after an idle spell — or a pair stayed
-      // pending): resolve its needed queue on the host side before relaunching, so every relaunch makes
-      // progress whatever the workers of the next dispatch do (exact codes; resolved ones rewrite the same)
-      if (k.qcount > 0) {
-        if (k.qcount > P.qcap) RET(TSW_EINVAL, "plan kernel queue overflow");
-        TRY(run_astar(c, c->d_Q, k.qcount, true, nullptr, nullptr));
-        TRY(check_err(c));
-      }
+    if (!coop) {
+      if (k.status != PLAN_NEED_QUERIES || k.qcount == 0 || k.qcount > P.qcap)
+        RET(TSW_EINVAL, "plan kernel stopped without resolvable next hops");
+      TRY(resolve_queue(c, c->d_Q, k.qcount));
       continue;
     }
-    if (k.status != PLAN_NEED_QUERIES || k.qcount == 0 || k.qcount > P.qcap)
-      RET(TSW_EINVAL, "plan kernel stopped without resolvable next hops");
-    TRY(resolve_queue(c, c->d_Q, k.qcount));
+    if (k.status != PLAN_NEED_QUERIES) RET(TSW_EINVAL, "plan kernel stopped without resolvable next hops");
+    if (c->h_flags[HF_ABORT]) {
+      // watchdog fired: finish this call in exit mode (host-side K3 passes at planner exits), from where
+      // the planner stopped; pairs the aborted workers left queued are unqueued first
+      HIPCHK(launch_reset_pending(c->d_nh, (uint64_t)c->tab_count * c->tstride, c->s));
+      HIPCHK(hipStreamSynchronize(c->s));
+      P.coop = 0;
+      PlanCtl resume = k;
+      resume.status = PLAN_RUNNING;
+      resume.qcount = 0;
+      TRY(upload_ctl(c, resume));
+      TRY(setup_dispatch(c, P, &D));
+      bound = 16ull * P.n + 4096ull * (resume.max_t + 1);
+      launches = 0;
+      continue;
+    }
+    // the planner gave up waiting (no worker left — they exit after an idle spell — or a pair stayed
+    // pending): resolve its needed queue on the host side before relaunching, so every relaunch makes
+    // progress whatever the workers of the next dispatch do (exact codes; resolved ones rewrite the same)
+    if (k.qcount > 0) {
+      if (k.qcount > P.qcap) RET(TSW_EINVAL, "plan kernel queue overflow");
+      TRY(run_astar(c, c->d_Q, k.qcount, true, nullptr, nullptr));
+      TRY(check_err(c));
+    }
   }
 }
 
@@ -597,19 +682,141 @@ static int run_plan(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
   return reset_pending_after(c, run_plan_impl(c, P, init));
 }
 
+// K4 spatial index: the tasks in Morton order of their (clamped) pickup points pxy (x | y << 16), cut into
+// chunks of 32 entries (k_plan's KCH) with static bounding boxes and counts (tsw_plan.h PlanArgs::kbox).
+// Padding entries of the last chunk stay TASK_TAKEN; no task still gives one (empty) chunk.
+struct TaskIndex {
+  std::vector<uint32_t> live, klt, kpos, kcnt;
+  std::vector<uint2> kbox;
+};
+
+static TaskIndex build_task_index(const std::vector<uint32_t>& pxy) {
+  constexpr uint32_t KCHH = 32;
+  const uint32_t m = (uint32_t)pxy.size(), nch = std::max<uint32_t>((m + KCHH - 1u) / KCHH, 1u);
+  TaskIndex ix{std::vector<uint32_t>((size_t)nch * KCHH, TASK_TAKEN), std::vector<uint32_t>((size_t)nch * KCHH, 0xFFFFFFFFu),
+               std::vector<uint32_t>(std::max<uint32_t>(m, 1u)), std::vector<uint32_t>(nch, 0u),
+               std::vector<uint2>(nch, make_uint2(0u, 0u))};
+  std::vector<std::pair<uint32_t, uint32_t>> ord(m);
+  for (uint32_t k = 0; k < m; ++k) ord[k] = {morton2(pxy[k] & 0xFFFFu, pxy[k] >> 16), k};
+  std::sort(ord.begin(), ord.end());
+  for (uint32_t pos = 0; pos < m; ++pos) {
+    const uint32_t k = ord[pos].second, xy = pxy[k], ch = pos / KCHH;
+    ix.live[pos] = xy;
+    ix.klt[pos] = k;
+    ix.kpos[k] = pos;
+    const uint32_t x = xy & 0xFFFFu, y = xy >> 16;
+    uint2& bx = ix.kbox[ch];
+    if (ix.kcnt[ch] == 0u) {
+      bx = make_uint2(xy, xy);
+    } else {
+      bx.x = std::min(bx.x & 0xFFFFu, x) | (std::min(bx.x >> 16, y) << 16);
+      bx.y = std::max(bx.y & 0xFFFFu, x) | (std::max(bx.y >> 16, y) << 16);
+    }
+    ++ix.kcnt[ch];
+  }
+  return ix;
+}
+
+// The plan's records, written by k_plan timestep-major (t * n + i), into the caller's agent-major arrays.
+static int download_records(tsw_ctx* c, uint32_t n, uint32_t t, size_t stride_t, tsw_rec* out, uint32_t* goal_out) {
+  std::vector<uint64_t> rec((size_t)t * n);
+  HIPCHK(hipMemcpyAsync(rec.data(), c->d_rec, rec.size() * 8, hipMemcpyDeviceToHost, c->s));
+  std::vector<uint32_t> grec;
+  if (goal_out) {
+    grec.resize((size_t)t * n);
+    HIPCHK(hipMemcpyAsync(grec.data(), c->d_grec, grec.size() * 4, hipMemcpyDeviceToHost, c->s));
+  }
+  HIPCHK(hipStreamSynchronize(c->s));
+  for (uint32_t tt = 0; tt < t; ++tt)
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint64_t r = rec[(size_t)tt * n + i];
+      tsw_rec& o = out[(size_t)i * stride_t + tt];
+      o.x = (uint16_t)(r & 0xFFFF);
+      o.y = (uint16_t)((r >> 16) & 0xFFFF);
+      o.state = (uint8_t)((r >> 32) & 0xFF);
+      o.pad[0] = o.pad[1] = o.pad[2] = 0;
+      if (goal_out) goal_out[(size_t)i * stride_t + tt] = grec[(size_t)tt * n + i];
+    }
+  return TSW_OK;
+}
+
+// The plan's inputs on the device: agent and task state and the K4 index, their buffers grown first.
+static int upload_plan_inputs(tsw_ctx* c, uint32_t n, uint32_t m, const std::vector<uint32_t>& vcell,
+                              const std::vector<uint32_t>& pick, const std::vector<uint32_t>& dlv, const TaskIndex& ix) {
+  const uint32_t nch = (uint32_t)ix.kcnt.size();
+  TRY(ensure_agents(c, std::max<uint32_t>(n, 1)));
+  if (!(c->d_live.holds(ix.live.size()) && c->d_pick.holds(ix.live.size()) && c->d_dlv.holds(ix.live.size()))) {
+    HIPCHK(hipStreamSynchronize(c->s));
+    HIPCHK(c->d_live.grow(ix.live.size()));
+    HIPCHK(c->d_pick.grow(ix.live.size()));
+    HIPCHK(c->d_dlv.grow(ix.live.size()));
+    if (!c->d_unused) HIPCHK(c->d_unused.alloc(1));
+  }
+  if (!(c->d_klt.holds(ix.live.size()) && c->d_kpos.holds(ix.live.size()))) {
+    HIPCHK(hipStreamSynchronize(c->s));
+    HIPCHK(c->d_klt.grow(ix.live.size()));
+    HIPCHK(c->d_kpos.grow(ix.live.size()));
+  }
+  if (!(c->d_kbox.holds(nch) && c->d_kcnt.holds(nch))) {
+    HIPCHK(hipStreamSynchronize(c->s));
+    HIPCHK(c->d_kbox.grow(nch));
+    HIPCHK(c->d_kcnt.grow(nch));
+  }
+  c->kchunks = nch;
+  if (n) {
+    HIPCHK(hipMemcpyAsync(c->d_v, vcell.data(), n * 4ull, hipMemcpyHostToDevice, c->s));
+    HIPCHK(hipMemcpyAsync(c->d_g, vcell.data(), n * 4ull, hipMemcpyHostToDevice, c->s));
+    HIPCHK(hipMemsetAsync(c->d_st, 0, n, c->s));
+    HIPCHK(hipMemsetAsync(c->d_task, 0xFF, n * 4ull, c->s));
+  }
+  HIPCHK(hipMemcpyAsync(c->d_live, ix.live.data(), ix.live.size() * 4ull, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemcpyAsync(c->d_klt, ix.klt.data(), ix.klt.size() * 4ull, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemcpyAsync(c->d_kpos, ix.kpos.data(), ix.kpos.size() * 4ull, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemcpyAsync(c->d_kbox, ix.kbox.data(), ix.kbox.size() * sizeof(uint2), hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemcpyAsync(c->d_kcnt, ix.kcnt.data(), ix.kcnt.size() * 4ull, hipMemcpyHostToDevice, c->s));
+  if (m) {
+    HIPCHK(hipMemcpyAsync(c->d_pick, pick.data(), m * 4ull, hipMemcpyHostToDevice, c->s));
+    HIPCHK(hipMemcpyAsync(c->d_dlv, dlv.data(), m * 4ull, hipMemcpyHostToDevice, c->s));
+  }
+  HIPCHK(hipMemcpyAsync(c->d_unused, &m, 4, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipStreamSynchronize(c->s));  // the host vectors may go once this returns
+  return TSW_OK;
+}
+
+// Coop mode: every task's pickup -> delivery path, resolved hop by hop by the workers in the background
+// (lowest priority): an agent that picks the task up finds its next hops already there. Also grows the hot
+// and the predicted chains' queues.
+static int queue_task_chains(tsw_ctx* c, uint32_t n, uint32_t m, const std::vector<uint32_t>& pick,
+                             const std::vector<uint32_t>& dlv) {
+  std::vector<AstarQuery> qt;
+  qt.reserve(m);
+  for (uint32_t k = 0; k < m; ++k)
+    if (pick[k] != dlv[k] && pick[k] != CELL_BAD && dlv[k] != CELL_BAD) qt.push_back(AstarQuery{pick[k], dlv[k], c->h_goal_tab[dlv[k]], 0u});
+  if (qt.size() > c->d_QT.cap) {
+    HIPCHK(hipStreamSynchronize(c->s));
+    HIPCHK(c->d_QT.grow(qt.size()));
+  }
+  if (!qt.empty()) {
+    HIPCHK(hipMemcpyAsync(c->d_QT, qt.data(), qt.size() * sizeof(AstarQuery), hipMemcpyHostToDevice, c->s));
+    HIPCHK(hipStreamSynchronize(c->s));
+  }
+  c->qt_count = (uint32_t)qt.size();
+  if (c->tun.hot_chains) TRY(grow_synced(c, c->d_QH, m));
+  // predictions: one per pickup (<= m) plus, with bit 1, one per goal change of a delivering agent;
+  // a full queue only stops predicting
+  const size_t qp = (size_t)m + 16u * (size_t)n * (c->tun.predict & 2u ? 8u : 0u);
+  if (c->tun.hot_chains && c->tun.predict) TRY(grow_synced(c, c->d_QP, qp));
+  return TSW_OK;
+}
+
+// validate -> index -> upload -> tables -> dispatch -> records
 static int plan_impl(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_task* tasks, uint32_t m,
               uint32_t max_t, tsw_rec* out, uint32_t* goal_out, uint32_t* out_T) {
   auto t0 = std::chrono::steady_clock::now();
   if (!out_T || (n && (!starts || !out)) || (m && !tasks)) RET(TSW_EINVAL, "null argument");
   if (max_t > (1u << 20)) RET(TSW_EINVAL, "max_t too large");
   TRY(set_device(c));
-  // K4 spatial index: tasks in Morton order of their (clamped) pickup points, cut into chunks of KCH = 32
-  // entries with static bounding boxes (tsw_plan.h PlanArgs::kbox)
-  constexpr uint32_t KCHH = 32;
-  const uint32_t nch = std::max<uint32_t>((m + KCHH - 1u) / KCHH, 1u);
-  std::vector<uint32_t> vcell(n), pick(m), dlv(m), pxy(m), live((size_t)nch * KCHH, TASK_TAKEN),
-      klt((size_t)nch * KCHH, 0xFFFFFFFFu), kpos(std::max<uint32_t>(m, 1u)), kcnt(nch, 0u);
-  std::vector<uint2> kbox(nch, make_uint2(0u, 0u));
+  std::vector<uint32_t> vcell(n), pick(m), dlv(m), pxy(m);
   std::vector<uint32_t> goalset;
   goalset.reserve(n + 2 * (size_t)m);
   for (uint32_t i = 0; i < n; ++i) {
@@ -631,73 +838,12 @@ static int plan_impl(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_
     if (pick[k] != CELL_BAD) goalset.push_back(pick[k]);
     if (dlv[k] != CELL_BAD) goalset.push_back(dlv[k]);
   }
-  {
-    auto morton = [](uint32_t xy) {
-      uint64_t z = 0;
-      for (uint32_t bt = 0; bt < 16u; ++bt)
-        z |= (uint64_t)((xy >> bt) & 1u) << (2u * bt) | (uint64_t)((xy >> (16u + bt)) & 1u) << (2u * bt + 1u);
-      return z;
-    };
-    std::vector<std::pair<uint64_t, uint32_t>> ord(m);
-    for (uint32_t k = 0; k < m; ++k) ord[k] = {morton(pxy[k]), k};
-    std::sort(ord.begin(), ord.end());
-    for (uint32_t pos = 0; pos < m; ++pos) {
-      const uint32_t k = ord[pos].second, xy = pxy[k], ch = pos / KCHH;
-      live[pos] = xy;
-      klt[pos] = k;
-      kpos[k] = pos;
-      const uint32_t x = xy & 0xFFFFu, y = xy >> 16;
-      uint2& bx = kbox[ch];
-      if (kcnt[ch] == 0u) {
-        bx = make_uint2(xy, xy);
-      } else {
-        bx.x = std::min(bx.x & 0xFFFFu, x) | (std::min(bx.x >> 16, y) << 16);
-        bx.y = std::max(bx.y & 0xFFFFu, x) | (std::max(bx.y >> 16, y) << 16);
-      }
-      ++kcnt[ch];
-    }
-  }
-  TRY(ensure_agents(c, std::max<uint32_t>(n, 1)));
-  if (!(c->d_live.holds(live.size()) && c->d_pick.holds(live.size()) && c->d_dlv.holds(live.size()))) {
-    HIPCHK(hipStreamSynchronize(c->s));
-    HIPCHK(c->d_live.grow(live.size()));
-    HIPCHK(c->d_pick.grow(live.size()));
-    HIPCHK(c->d_dlv.grow(live.size()));
-    if (!c->d_unused) HIPCHK(c->d_unused.alloc(1));
-  }
-  if (!(c->d_klt.holds(live.size()) && c->d_kpos.holds(live.size()))) {
-    HIPCHK(hipStreamSynchronize(c->s));
-    HIPCHK(c->d_klt.grow(live.size()));
-    HIPCHK(c->d_kpos.grow(live.size()));
-  }
-  if (!(c->d_kbox.holds(nch) && c->d_kcnt.holds(nch))) {
-    HIPCHK(hipStreamSynchronize(c->s));
-    HIPCHK(c->d_kbox.grow(nch));
-    HIPCHK(c->d_kcnt.grow(nch));
-  }
-  c->kchunks = nch;
+  const TaskIndex ix = build_task_index(pxy);
+  TRY(upload_plan_inputs(c, n, m, vcell, pick, dlv, ix));
   const size_t stride_t = (size_t)max_t + 1;
   const size_t recs = stride_t * std::max<uint32_t>(n, 1);
   TRY(grow_synced(c, c->d_rec, recs));
   if (goal_out) TRY(grow_synced(c, c->d_grec, recs));
-  // agent + task state
-  if (n) {
-    HIPCHK(hipMemcpyAsync(c->d_v, vcell.data(), n * 4ull, hipMemcpyHostToDevice, c->s));
-    HIPCHK(hipMemcpyAsync(c->d_g, vcell.data(), n * 4ull, hipMemcpyHostToDevice, c->s));
-    HIPCHK(hipMemsetAsync(c->d_st, 0, n, c->s));
-    HIPCHK(hipMemsetAsync(c->d_task, 0xFF, n * 4ull, c->s));
-  }
-  HIPCHK(hipMemcpyAsync(c->d_live, live.data(), live.size() * 4ull, hipMemcpyHostToDevice, c->s));
-  HIPCHK(hipMemcpyAsync(c->d_klt, klt.data(), klt.size() * 4ull, hipMemcpyHostToDevice, c->s));
-  HIPCHK(hipMemcpyAsync(c->d_kpos, kpos.data(), kpos.size() * 4ull, hipMemcpyHostToDevice, c->s));
-  HIPCHK(hipMemcpyAsync(c->d_kbox, kbox.data(), kbox.size() * sizeof(uint2), hipMemcpyHostToDevice, c->s));
-  HIPCHK(hipMemcpyAsync(c->d_kcnt, kcnt.data(), kcnt.size() * 4ull, hipMemcpyHostToDevice, c->s));
-  if (m) {
-    HIPCHK(hipMemcpyAsync(c->d_pick, pick.data(), m * 4ull, hipMemcpyHostToDevice, c->s));
-    HIPCHK(hipMemcpyAsync(c->d_dlv, dlv.data(), m * 4ull, hipMemcpyHostToDevice, c->s));
-  }
-  HIPCHK(hipMemcpyAsync(c->d_unused, &m, 4, hipMemcpyHostToDevice, c->s));
-  HIPCHK(hipStreamSynchronize(c->s));  // host vectors above go out of scope only at return, but keep it simple
   auto tphase = [&](const char* what) {  // diagnostics (TSW_PLAN_DEBUG): host-side phases of the call
     if (c->tun.plan_debug)
       fprintf(stderr, "[plan] %s at %.1f ms\n", what,
@@ -712,28 +858,7 @@ static int plan_impl(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_
   c->qt_count = 0;
   if (c->tun.coop && !c->resolver && !eager_policy(c, 0)) {
     TRY(ensure_coop(c, n, max_t));
-    if (c->tun.task_chains && m) {
-      // every task's pickup -> delivery path, resolved hop by hop by the workers in the background
-      // (lowest priority): an agent that picks the task up finds its next hops already there
-      std::vector<AstarQuery> qt;
-      qt.reserve(m);
-      for (uint32_t k = 0; k < m; ++k)
-        if (pick[k] != dlv[k] && pick[k] != CELL_BAD && dlv[k] != CELL_BAD) qt.push_back(AstarQuery{pick[k], dlv[k], c->h_goal_tab[dlv[k]], 0u});
-      if (qt.size() > c->d_QT.cap) {
-        HIPCHK(hipStreamSynchronize(c->s));
-        HIPCHK(c->d_QT.grow(qt.size()));
-      }
-      if (!qt.empty()) {
-        HIPCHK(hipMemcpyAsync(c->d_QT, qt.data(), qt.size() * sizeof(AstarQuery), hipMemcpyHostToDevice, c->s));
-        HIPCHK(hipStreamSynchronize(c->s));
-      }
-      c->qt_count = (uint32_t)qt.size();
-      if (c->tun.hot_chains) TRY(grow_synced(c, c->d_QH, m));
-      // predictions: one per pickup (<= m) plus, with bit 1, one per goal change of a delivering agent;
-      // a full queue only stops predicting
-      const size_t qp = (size_t)m + 16u * (size_t)n * (c->tun.predict & 2u ? 8u : 0u);
-      if (c->tun.hot_chains && c->tun.predict) TRY(grow_synced(c, c->d_QP, qp));
-    }
+    if (c->tun.task_chains && m) TRY(queue_task_chains(c, n, m, pick, dlv));
   }
   PlanArgs P = plan_args(c, n, m, MODE_MAPD, goal_out != nullptr);
   PlanCtl init{};
@@ -748,26 +873,7 @@ static int plan_impl(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_
   const uint32_t t = c->h_ctl->t;
   c->st.steps += t;
   *out_T = t;
-  if (n) {
-    std::vector<uint64_t> rec((size_t)t * n);
-    HIPCHK(hipMemcpyAsync(rec.data(), c->d_rec, rec.size() * 8, hipMemcpyDeviceToHost, c->s));
-    std::vector<uint32_t> grec;
-    if (goal_out) {
-      grec.resize((size_t)t * n);
-      HIPCHK(hipMemcpyAsync(grec.data(), c->d_grec, grec.size() * 4, hipMemcpyDeviceToHost, c->s));
-    }
-    HIPCHK(hipStreamSynchronize(c->s));
-    for (uint32_t tt = 0; tt < t; ++tt)
-      for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t r = rec[(size_t)tt * n + i];
-        tsw_rec& o = out[(size_t)i * stride_t + tt];
-        o.x = (uint16_t)(r & 0xFFFF);
-        o.y = (uint16_t)((r >> 16) & 0xFFFF);
-        o.state = (uint8_t)((r >> 32) & 0xFF);
-        o.pad[0] = o.pad[1] = o.pad[2] = 0;
-        if (goal_out) goal_out[(size_t)i * stride_t + tt] = grec[(size_t)tt * n + i];
-      }
-  }
+  if (n) TRY(download_records(c, n, t, stride_t, out, goal_out));
   resolve_timing(c);
   c->st.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return TSW_OK;

@@ -43,12 +43,6 @@ static bool mg_selected(const tsw_ctx* c, size_t k) {
   return bfs_mg_lds_bytes(c->G.W, c->G.H, c->nbp) <= (size_t)c->max_lds;
 }
 
-static uint32_t morton2(uint32_t x, uint32_t y) {
-  uint32_t z = 0;
-  for (uint32_t b = 0; b < 16u; ++b) z |= ((x >> b) & 1u) << (2u * b) | ((y >> b) & 1u) << (2u * b + 1u);
-  return z;
-}
-
 // k_bfs_mg launch order: goals grouped by (cell parity, Morton order) into groups of <= 16 (one
 // parity per group: the kernel advances all of a group's fronts on one checkerboard colour per
 // level), groups ordered longest-first by the eccentricity bound of their first goal (LPT, as

@@ -130,7 +130,7 @@ __device__ __forceinline__ int worker_claim(CoopCtl* cc, uint32_t* idx, bool tak
     for (uint32_t k = 0;; ++k) {
       // host watchdog abort (pinned host memory, read over the host link: rarely)
       if ((k & 255u) == 255u && hflags &&
-          __hip_atomic_load(&hflags[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)
+          __hip_atomic_load(&hflags[HF_ABORT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)
         return -1;
       if (wall_clock64() - t0 > idle_ticks) return -1;  // idle this long (5 s): safety exit
       if (k < 8) {

@@ -28,7 +28,7 @@ ABATCH = 16    # widest batch
 # product, then the diagnostic library with TSW_AB_FLAGS = 0 / 4 / 32
 VARIANTS = [("product", None), ("diag", 0), ("diag-one", 4), ("diag-cap4", 32)]
 
-# the two stderr lines of run_plan_impl (tsw_plan_host.hip) under TSW_PLAN_DEBUG that _diag() reads:
+# the two stderr lines of plan_debug_report (tsw_plan_host.hip) under TSW_PLAN_DEBUG that _diag() reads:
 #   "[k_plan] assign us: ... | sections %llu batches %llu accepted %llu"
 #   "[k_plan] assign scan us: ... | chunk-agent pairs %llu chunks %llu scanning waves %llu list rounds %llu | batch widths
 #    1: %llu 2-4: %llu 5-8: %llu 9-16: %llu"

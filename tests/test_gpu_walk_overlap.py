@@ -25,7 +25,7 @@ W, H, N_AGENTS, N_TASKS, MAX_T = 24, 14, 70, 2000, 300
 SEED = 6
 STEPS = MAX_T + 1  # PRE1 sections of the plan: one per record, the last one's step ends at the horizon
 
-# run_plan_impl (tsw_plan_host.hip) under TSW_PLAN_DEBUG:
+# plan_debug_report (tsw_plan_host.hip) under TSW_PLAN_DEBUG:
 #   "[k_plan] PRE1 publish us ... | walk-ahead steps in PRE1 %llu left to RULES %llu done in RULES %llu
 #    walkers us %.0f wave 0 first %llu"
 _RE_WALK = re.compile(r"\[k_plan\] PRE1 publish us .*\| walk-ahead steps in PRE1 (\d+) left to RULES (\d+) "

@@ -60,7 +60,7 @@ def check_own_cells(tabs, goals, v, g, what: str):
     assert bad.size == 0, f"{what}: {bad.size} agents' own codes unresolved, first agent {bad[0]}: 0x{codes[bad[0]]:02x}"
 
 
-# The two stderr lines of run_plan_impl (tsw_plan_host.hip) under TSW_PLAN_DEBUG that _diag() depends on:
+# The two stderr lines of worker_args and coop_debug_report (tsw_plan_host.hip) under TSW_PLAN_DEBUG that _diag() depends on:
 #   fprintf(stderr, "[k_plan] workers: %u waves (%u per workgroup), g-scores %u, heap %u entries, DAG exit %u, %u B LDS each\n", ...)
 #   fprintf(stderr, "[k_plan] worker A* ms (queries, pops): ... | tier-2 hand-offs %llu tier-3 %llu | detour staging %.1f ms (%u)\n", ...)
 _RE_WORKERS = re.compile(r"\[k_plan\] workers: (\d+) waves \((\d+) per workgroup\), g-scores (\d+), heap (\d+) entries, "
