@@ -52,7 +52,10 @@ __global__ void __launch_bounds__(1024) k_bfs(DevGrid G, const uint32_t* __restr
   uint32_t* FR = smem + 3 * nwp;
   uint16_t* Dl = reinterpret_cast<uint16_t*>(smem + 4 * nwp);
   const float invWw = 1.0f / (float)Ww;
-  const bool vec_ok = (dstride % 8u) == 0;
+  // 16-B table stores / 8-B code stores need every table (base + slot * stride) aligned, not the stride
+  // alone: the caller's memory is only promised as uint16_t* / uint8_t* (run_bfs tests the same for vec16)
+  const bool vec_ok = (dstride % 8u) == 0 && (reinterpret_cast<uintptr_t>(dist_base) & 15u) == 0;
+  const bool nh_vec = (nstride % 8u) == 0 && (reinterpret_cast<uintptr_t>(nh_base) & 7u) == 0;
 
   for (uint32_t t = tid; t < nw; t += bd) FR[t] = G.freebits[t];
 
@@ -139,7 +142,10 @@ __global__ void __launch_bounds__(1024) k_bfs(DevGrid G, const uint32_t* __restr
     } else if (LDS_TABLE) {
       for (uint32_t c = tid; c < ncell; c += bd) Dg[c] = Dl[c];
     }
-    if (NHg) {
+    if (NHg && !nh_vec) {
+      for (uint32_t c = tid; c < ncell; c += bd)
+        NHg[c] = classify_cell(D, c, G.nbmask[c], W, goal, gx, gy);
+    } else if (NHg) {
       for (uint32_t c8 = tid; c8 < ncp / 8u; c8 += bd) {
         const uint64_t m8 = reinterpret_cast<const uint64_t*>(G.nbmask)[c8];
         uint64_t codes = 0;

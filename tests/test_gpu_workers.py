@@ -16,40 +16,10 @@ import pytest
 
 import worker_cases as wc
 from p2p_distributed_tswap_amd import Planner, TSW_HOST_ASTAR_OFF, maps
-from worker_cases import ASTAR as _ASTAR, NH_STAY, NH_UNKNOWN, MapRef
+from table_io_cases import check_store  # the store audit, shared with the table entry-point tests
+from worker_cases import NH_STAY, MapRef
 
 pytestmark = pytest.mark.gpu
-
-
-def check_store(p, ref: MapRef, goals, what: str):
-    """Everything the store holds for `goals`: every code != 0xFF at a free cell equals the oracle's (none
-    skipped or sampled; a code left pending fails too), blocked cells hold 0xFF. Returns the tables (goal
-    order: np.unique(goals)) and the number of A*-decided codes that were checked."""
-    goals = np.unique(np.asarray(goals, dtype=np.uint32))
-    tabs = p.next_hop_tables(goals)
-    pairs, where = [], []
-    for k, goal in enumerate(goals):
-        got, k1 = tabs[k], ref.k1(int(goal))
-        assert (got[~ref.free] == NH_UNKNOWN).all(), f"{what}: goal {goal}: a blocked cell holds a code"
-        res = ref.free & (got != NH_UNKNOWN)
-        bad = np.flatnonzero(res & (k1 != _ASTAR) & (got != k1))
-        assert bad.size == 0, (f"{what}: goal {goal}: {bad.size} BFS-decided codes differ, first cell {bad[0]} "
-                               f"got {got[bad[0]]} want {k1[bad[0]]}")
-        # cells K1 alone decides are never left unresolved
-        assert not (ref.free & (k1 != _ASTAR) & (got == NH_UNKNOWN)).any(), f"{what}: goal {goal}: K1 code missing"
-        for c in np.flatnonzero(res & (k1 == _ASTAR)):
-            pairs.append((int(c), int(goal)))
-            where.append(k)
-    want = ref.astar_codes(pairs)
-    got = np.array([tabs[k][c] for (c, _), k in zip(pairs, where)], dtype=np.uint8)
-    bad = np.flatnonzero(got != want)
-    if bad.size:
-        c, goal = pairs[bad[0]]
-        delta, multi = wc.detour_classes(ref.og, ref.cells, goal)
-        pytest.fail(f"{what}: {bad.size} of {len(pairs)} A*-decided codes in the store differ from get_path; first "
-                    f"(cell {c}, goal {goal}): got {got[bad[0]]} want {want[bad[0]]}, delta {delta[c]}, "
-                    f"multi-candidate {bool(multi[c])}")
-    return tabs, goals, len(pairs)
 
 
 def check_own_cells(tabs, goals, v, g, what: str):
