@@ -67,7 +67,8 @@ extern "C" {
  * 7: tsw_opts.reserved became host_astar, tsw_stats gained host_astar_queries / host_astar_used /
  * host_astar_ms, tsw_host_next_hop_codes; 8: tsw_nearby, tsw_decide_fleet. Still 8: tsw_fleet_apply and
  * tsw_fleet_run, and after them tsw_fleet_mapd, were added without touching a struct or an existing
- * signature; a caller that wants them looks the symbols up (dlsym) instead of comparing the revision. */
+ * signature, and so were tsw_audit_records and tsw_audit_records_device (one new struct, tsw_audit); a
+ * caller that wants them looks the symbols up (dlsym) instead of comparing the revision. */
 #define TSW_ABI_VERSION 8
 
 /* AgentState discriminants in declaration order (src/map/agent.rs:9-15) */
@@ -348,6 +349,50 @@ int tsw_fleet_run(tsw_ctx *ctx, uint32_t *v, uint32_t *g, uint32_t n, uint32_t r
 int tsw_fleet_mapd(tsw_ctx *ctx, const tsw_point *starts, uint32_t n, const tsw_task *tasks, uint32_t m,
                    uint32_t radius, uint32_t max_t, tsw_rec *out, uint32_t *goal_out, uint32_t *task_out,
                    uint32_t *out_T, uint32_t *stalled);
+
+/* K6: the audit of plan records, on the device. rec: n rows of records as every plan entry point writes
+ * them (tsw_plan_mapd, tsw_fleet_mapd), agent-major: agent i's column t is rec[i*stride + t]; only columns
+ * 0 .. T-1 are read and the pad bytes are ignored. The cell of a record is (x, y); a record is ON-GRID when
+ * x < w && y < h; blocked cells are the context's grid's. Every quantity that looks at column t-1 is 0 in
+ * column 0.
+ * col (may be NULL): T * TSW_AUDIT_NCOL words, col[t*TSW_AUDIT_NCOL + k] =
+ *   k 0-3  agents whose state is 0 .. 3 (TSW_PICKING .. TSW_IDLE)
+ *   k 4    bad_state: agents with state > 3
+ *   k 5    moved: agents whose (x, y) differs from column t-1
+ *   k 6    deliveries: agents TSW_DELIVERED at t that were not at t-1 (at t = 0: TSW_DELIVERED)
+ *   k 7    colocations: on-grid agents that are not the smallest index on their cell (= on-grid agents minus
+ *          the distinct cells among them: the agents beyond the first on a cell)
+ *   k 8    swaps: agents on-grid at t-1 and t that step from a to a 4-neighbour b while some other agent steps
+ *          from b to a in the same transition. Agents are counted, not pairs; co-located agents that all take
+ *          the edge all count.
+ *   k 9    jumps: agents with |dx| + |dy| > 1 against column t-1 (coordinates only: diagonal steps, teleports)
+ *   k 10   off_map: agents whose record is off-grid or on a blocked cell
+ * agent (may be NULL): n * TSW_AUDIT_NAGENT words, agent[i*TSW_AUDIT_NAGENT + k] = 0 moves, 1 deliveries,
+ *   2 columns in which i is charged with any violation kind, 3 the first such column (0xFFFFFFFF if none).
+ * Violation kinds, the order of first_t / first_agent: 0 colocation, 1 swap, 2 jump, 3 off_map, 4 bad_state.
+ * sum: the column sums and the first violations; computed whether or not col and agent are given.
+ * moving_columns is what the bench line reports as moving timesteps.
+ * TSW_EINVAL before anything is launched, the outputs untouched: a NULL sum; a NULL rec with n > 0 && T > 0;
+ * stride < T; T > 2^20 + 1; a context inside its own resolver. n == 0 or T == 0: TSW_OK, an all-zero sum with
+ * first_t / first_agent 0xFFFFFFFF, col and agent untouched. TSW_ENOMEM when the scratch does not fit (the
+ * transpose alone is 4 B per record). The call reads the context's grid only: the table store, the queues
+ * and the stats are untouched, and a plan after an audit equals a plan without one.
+ * tsw_audit_records_device: the same with the records in DEVICE memory (e.g. a torch tensor's data_ptr on
+ * the context's device), read in place with their stride; sum, col and agent are host memory in both forms. */
+#define TSW_AUDIT_NCOL 11u   /* words per column in col[]   */
+#define TSW_AUDIT_NAGENT 4u  /* words per agent in agent[]  */
+#define TSW_AUDIT_NKIND 5u   /* violation kinds, above      */
+typedef struct {
+    uint64_t state_steps[4];   /* agent-columns per AgentState discriminant */
+    uint64_t bad_state, moves, deliveries, colocations, swaps, jumps, off_map;
+    uint32_t moving_columns;   /* columns t >= 1 with moves > 0 */
+    uint32_t first_t[5];       /* per kind: smallest column with a violation, 0xFFFFFFFF if none */
+    uint32_t first_agent[5];   /* smallest agent index charged with it in that column */
+} tsw_audit;
+int tsw_audit_records(tsw_ctx *ctx, const tsw_rec *rec, uint32_t n, uint32_t T, uint32_t stride,
+                      tsw_audit *sum, uint32_t *col, uint32_t *agent);
+int tsw_audit_records_device(tsw_ctx *ctx, const tsw_rec *dev_rec, uint32_t n, uint32_t T,
+                             uint32_t stride, tsw_audit *sum, uint32_t *col, uint32_t *agent);
 
 /* K1: BFS distance tables for k goal cells, u16 per cell, row-major
  * (TSW_DIST_INF for blocked/unreachable). out: host buffer k*w*h. */

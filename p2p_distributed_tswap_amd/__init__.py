@@ -40,6 +40,9 @@ TSW_HOST_ASTAR_OFF = 0xFFFFFFFF  # tsw_opts.host_astar: no host A* service
 TSW_F_EAGER_NEXTHOP, TSW_F_LAZY_NEXTHOP, TSW_F_EXIT_MODE = 1, 2, 4
 # TswapAction (bin/decentralized/agent.rs:321-326), include/tswap.h TSW_ACT_*
 TSW_ACT_MOVE, TSW_ACT_GOAL_SWAP, TSW_ACT_ROTATION, TSW_ACT_WAIT = 0, 1, 2, 3
+# tsw_audit_records (include/tswap.h): words per column / per agent, violation kinds
+TSW_AUDIT_NCOL, TSW_AUDIT_NAGENT, TSW_AUDIT_NKIND = 11, 4, 5
+AUDIT_KINDS = ("colocation", "swap", "jump", "off_map", "bad_state")
 DIST_INF = 0xFFFF
 
 
@@ -117,6 +120,22 @@ class Stats(ctypes.Structure):
         return d
 
 
+class Audit(ctypes.Structure):
+    """tsw_audit (include/tswap.h)."""
+    _fields_ = [
+        ("state_steps", ctypes.c_uint64 * 4), ("bad_state", ctypes.c_uint64), ("moves", ctypes.c_uint64),
+        ("deliveries", ctypes.c_uint64), ("colocations", ctypes.c_uint64), ("swaps", ctypes.c_uint64),
+        ("jumps", ctypes.c_uint64), ("off_map", ctypes.c_uint64), ("moving_columns", ctypes.c_uint32),
+        ("first_t", ctypes.c_uint32 * 5), ("first_agent", ctypes.c_uint32 * 5),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        for k in ("state_steps", "first_t", "first_agent"):
+            d[k] = list(d[k])
+        return d
+
+
 # every symbol declared in include/tswap.h (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
     "tsw_create", "tsw_destroy", "tsw_last_error", "tsw_plan_mapd", "tsw_plan_mapd_trace",
@@ -125,7 +144,7 @@ EXPORTED_SYMBOLS = (
     "tsw_clear_tables", "tsw_get_stats", "tsw_reset_stats", "tsw_set_timing", "tsw_probe_round_floors",
     "tsw_abi_version", "tsw_plan_mapd_resolved", "tsw_next_hop_codes", "tsw_build_id",
     "tsw_host_next_hop_codes", "tsw_nearby", "tsw_decide_fleet", "tsw_fleet_apply", "tsw_fleet_run",
-    "tsw_fleet_mapd",
+    "tsw_fleet_mapd", "tsw_audit_records", "tsw_audit_records_device",
 )
 
 # tsw_resolve_fn (include/tswap.h): int (*)(void *user, uint32_t k, const uint32_t *start,
@@ -178,6 +197,10 @@ def load_library(path: str = LIB_PATH):
     lib.tsw_fleet_run.restype = ctypes.c_int
     lib.tsw_fleet_mapd.argtypes = [vp, P(_Point), u32, P(_Task), u32, u32, u32, P(_Rec), P(u32), P(u32), P(u32), P(u32)]
     lib.tsw_fleet_mapd.restype = ctypes.c_int
+    lib.tsw_audit_records.argtypes = [vp, P(_Rec), u32, u32, u32, P(Audit), P(u32), P(u32)]
+    lib.tsw_audit_records.restype = ctypes.c_int
+    lib.tsw_audit_records_device.argtypes = [vp, vp, u32, u32, u32, P(Audit), P(u32), P(u32)]
+    lib.tsw_audit_records_device.restype = ctypes.c_int
     lib.tsw_dist_tables.argtypes = [vp, P(u32), u32, P(ctypes.c_uint16)]
     lib.tsw_dist_tables_device.argtypes = [vp, P(u32), u32, vp]
     lib.tsw_import_tables_device.argtypes = [vp, P(u32), u32, vp]
@@ -529,6 +552,41 @@ class Planner:
         if trace:
             return rec, goals[:n, :t].copy(), tks[:n, :t].copy(), bool(stalled.value)
         return rec, bool(stalled.value)
+
+    # --- audit ------------------------------------------------------------
+    def _audit(self, call, n, T, col, agents):
+        sm = Audit()
+        cw = np.zeros((T, TSW_AUDIT_NCOL), dtype=np.uint32) if col else None
+        aw = np.zeros((n, TSW_AUDIT_NAGENT), dtype=np.uint32) if agents else None
+        if aw is not None:
+            aw[:, 3] = 0xFFFFFFFF  # what an agent without a violation reports (the call writes nothing for n * T == 0)
+        self._check(call(ctypes.byref(sm), _u32p(cw) if col else None, _u32p(aw) if agents else None))
+        out = sm.as_dict()
+        if col:
+            out["col"] = cw
+        if agents:
+            out["agents"] = aw
+        return out
+
+    def audit(self, rec, col: bool = False, agents: bool = False) -> dict:
+        """tsw_audit_records: conflicts, legality and deliveries of plan records, counted on the device.
+        rec: the packed (n, T) uint64 array plan_mapd_arrays and fleet_mapd return (x | y<<16 | state<<32;
+        higher bits are ignored). Returns the summary (tsw_audit's fields: state_steps, bad_state, moves,
+        deliveries, colocations, swaps, jumps, off_map, moving_columns, first_t / first_agent per
+        AUDIT_KINDS), plus "col" (T, 11) uint32 with col=True and "agents" (n, 4) uint32 with agents=True
+        (the columns as include/tswap.h lists them)."""
+        rec = np.ascontiguousarray(rec, dtype=np.uint64)
+        if rec.ndim != 2:
+            raise TswapError(TSW_EINVAL, "rec must be an (n, T) array")
+        n, T = rec.shape
+        rp = rec.ctypes.data_as(ctypes.POINTER(_Rec))
+        return self._audit(lambda s, c, a: self._lib.tsw_audit_records(self._ctx, rp, n, T, T, s, c, a), n, T, col, agents)
+
+    def audit_device(self, ptr: int, n: int, T: int, stride: int, col: bool = False, agents: bool = False) -> dict:
+        """tsw_audit_records_device: as audit, the records in device memory on the context's device (e.g. a
+        torch int64 tensor's data_ptr), agent i's column t at ptr + 8 * (i * stride + t)."""
+        return self._audit(lambda s, c, a: self._lib.tsw_audit_records_device(self._ctx, ptr, n, T, stride, s, c, a),
+                           int(n), int(T), col, agents)
 
     # --- get_path -----------------------------------------------------------
     def get_path_next(self, start: np.ndarray, goal: np.ndarray):

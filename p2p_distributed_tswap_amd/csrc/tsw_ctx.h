@@ -1,7 +1,8 @@
-// tsw_ctx.h — the host runtime's context (struct tsw_ctx behind include/tswap.h) and what its five
+// tsw_ctx.h — the host runtime's context (struct tsw_ctx behind include/tswap.h) and what its six
 // translation units share: tsw_ctx.hip (create / destroy, tunables, stats), tsw_tables.hip (K1 and the
 // goal-table store), tsw_query.hip (K3 scratch, queue and passes), tsw_plan_host.hip (the plan runner and
-// its host A* service) and tsw_fleet_host.hip (decide and the fleet entry points). Host code only; every
+// its host A* service), tsw_fleet_host.hip (decide and the fleet entry points) and tsw_audit_host.hip (the
+// audit of plan records). Host code only; every
 // device buffer of the context is a DevBuf / PinnedBuf member (tsw_buf.h) and is freed with it.
 // Nothing here depends on the build flavour: only tsw_ctx.hip is compiled per flavour.
 #pragma once
@@ -262,6 +263,11 @@ struct tsw_ctx {
   // [2] tsw_fleet_run's records (v_rec | g_rec) or tsw_fleet_mapd's (out | goal_out | task_out)
   DevBuf<uint32_t> d_fleet[3];
   PinnedBuf<uint32_t> h_fleet;  // staging of tsw_decide_fleet: v | g up, act | cell | partner | part_off down
+  // tsw_audit_records scratch (grow-only): the uploaded records (T per row), the column-major transpose
+  // pass A writes (T * n words), first | col | agent (the outputs), pass B's occupancy tables outside LDS
+  DevBuf<unsigned long long> d_aud_rec;
+  DevBuf<uint32_t> d_aud_cid, d_aud_out;
+  DevBuf<unsigned long long> d_aud_tab;
 
   // stats / timing
   tsw_stats st{};

@@ -56,6 +56,10 @@ pub const TSW_ACT_GOAL_SWAP: u32 = 1;
 pub const TSW_ACT_ROTATION: u32 = 2;
 pub const TSW_ACT_WAIT: u32 = 3;
 
+pub const TSW_AUDIT_NCOL: u32 = 11;
+pub const TSW_AUDIT_NAGENT: u32 = 4;
+pub const TSW_AUDIT_NKIND: u32 = 5;
+
 /// `tsw_resolve_fn`: the caller's K3 for `tsw_plan_mapd_resolved` — fill `code[i]` (0..3 S,E,N,W,
 /// 4 stay) for get_path(start[i], goal[i]) and return 0 (e.g. send each pair to its goal's owner).
 pub type TswResolveFn =
@@ -78,6 +82,24 @@ pub struct TswPoint {
 pub struct TswTask {
     pub pickup: TswPoint,
     pub delivery: TswPoint,
+}
+
+/// `tsw_audit`: the summary of `tsw_audit_records` (column sums and the first violation per kind:
+/// 0 colocation, 1 swap, 2 jump, 3 off_map, 4 bad_state).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct TswAudit {
+    pub state_steps: [u64; 4],
+    pub bad_state: u64,
+    pub moves: u64,
+    pub deliveries: u64,
+    pub colocations: u64,
+    pub swaps: u64,
+    pub jumps: u64,
+    pub off_map: u64,
+    pub moving_columns: u32,
+    pub first_t: [u32; 5],
+    pub first_agent: [u32; 5],
 }
 
 #[repr(C)]
@@ -172,6 +194,10 @@ extern "C" {
     pub fn tsw_fleet_mapd(ctx: *mut TswCtx, starts: *const TswPoint, n: u32, tasks: *const TswTask, m: u32,
                           radius: u32, max_t: u32, out: *mut TswRec, goal_out: *mut u32, task_out: *mut u32,
                           out_t: *mut u32, stalled: *mut u32) -> c_int;
+    pub fn tsw_audit_records(ctx: *mut TswCtx, rec: *const TswRec, n: u32, t: u32, stride: u32, sum: *mut TswAudit,
+                             col: *mut u32, agent: *mut u32) -> c_int;
+    pub fn tsw_audit_records_device(ctx: *mut TswCtx, dev_rec: *const TswRec, n: u32, t: u32, stride: u32,
+                                    sum: *mut TswAudit, col: *mut u32, agent: *mut u32) -> c_int;
     pub fn tsw_dist_tables(ctx: *mut TswCtx, goals: *const u32, k: u32, out: *mut u16) -> c_int;
     pub fn tsw_dist_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_out: *mut u16) -> c_int;
     pub fn tsw_import_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_tables: *const u16) -> c_int;
