@@ -397,6 +397,14 @@ WorkerCfg worker_config(const DevGrid& G, int num_cu, uint32_t n_agents, uint32_
 // with W (coop mode) workgroups 1..worker_blocks run W->wpb K3 worker waves each.
 hipError_t launch_plan(const PlanArgs& P, PlanArgs* d_args, const WorkerArgs* W, uint32_t worker_blocks, size_t lds,
                        uint32_t block, hipStream_t s);
+// One instantiation of k_plan, launched. AG: every agent array in LDS; OC: the occupancy grid; MUL: with OC, the
+// movement rounds' MU words too; PG (!AG): the fixed subset PART_PG of the agent arrays. Defined in tsw_plan_kernel.h
+// and explicitly instantiated once per flag tuple, each in a translation unit of its own (tsw_plan_v0 .. v6.hip: an
+// instantiation takes minutes of hipcc, and the build compiles them in parallel). launch_plan's ladder is the one
+// place that maps a PlanArgs to its tuple; a tuple without a translation unit does not link.
+template <bool AG, bool OC, bool MUL, bool PG>
+hipError_t launch_plan_t(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
+                         hipStream_t s);
 
 }  // namespace tsw
 

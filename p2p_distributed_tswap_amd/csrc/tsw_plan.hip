@@ -1,23 +1,9 @@
 // tsw_plan.hip — host side of the persistent plan kernel k_plan (tsw_plan_kernel.h): LDS sizing, the
-// occupancy build and the launch, which picks one of the k_plan instantiations compiled in tsw_plan_v*.hip.
-#include "tsw_plan_kernel.h"
+// occupancy build and the launch, which picks one of the k_plan instantiations (launch_plan_t, tsw_plan.h)
+// that tsw_plan_v*.hip compile.
+#include "tsw_plan_dev.h"
 
 namespace tsw {
-
-hipError_t launch_plan_v0(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
-                          hipStream_t s);
-hipError_t launch_plan_v1(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
-                          hipStream_t s);
-hipError_t launch_plan_v2(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
-                          hipStream_t s);
-hipError_t launch_plan_v3(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
-                          hipStream_t s);
-hipError_t launch_plan_v4(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
-                          hipStream_t s);
-hipError_t launch_plan_v5(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
-                          hipStream_t s);
-hipError_t launch_plan_v6(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
-                          hipStream_t s);
 
 // occupancy in the k_plan encoding: lowest agent index | OCC_FLAG if shared, OCC_NONE if empty
 __global__ void k_occ_init(uint32_t* occ, uint32_t* cnt, uint32_t ncell) {
@@ -83,13 +69,14 @@ hipError_t launch_plan(const PlanArgs& P, PlanArgs* d_args, const WorkerArgs* W,
   const bool mu = P.occ_lds && P.mu_lds;
   // the kernel reads its arguments from d_args (stream order: after the previous dispatch has finished)
   if (hipError_t e = hipMemcpyAsync(d_args, &P, sizeof(PlanArgs), hipMemcpyHostToDevice, s); e != hipSuccess) return e;
-  if (P.agents_lds && mu) return launch_plan_v0(d_args, A, grid, lds, block, s);
-  if (P.agents_lds && P.occ_lds) return launch_plan_v1(d_args, A, grid, lds, block, s);
-  if (P.agents_lds) return launch_plan_v2(d_args, A, grid, lds, block, s);
-  if (P.part_lds == PART_PG && !P.occ_lds) return launch_plan_v3(d_args, A, grid, lds, block, s);
-  if (mu) return launch_plan_v4(d_args, A, grid, lds, block, s);
-  if (P.occ_lds) return launch_plan_v5(d_args, A, grid, lds, block, s);
-  return launch_plan_v6(d_args, A, grid, lds, block, s);
+  // k_plan<AG, OC, MUL, PG> by what the host placed in LDS; the tests stand in this order (tsw_plan_v0 .. v6.hip)
+  if (P.agents_lds && mu) return launch_plan_t<true, true, true, false>(d_args, A, grid, lds, block, s);
+  if (P.agents_lds && P.occ_lds) return launch_plan_t<true, true, false, false>(d_args, A, grid, lds, block, s);
+  if (P.agents_lds) return launch_plan_t<true, false, false, false>(d_args, A, grid, lds, block, s);
+  if (P.part_lds == PART_PG && !P.occ_lds) return launch_plan_t<false, false, false, true>(d_args, A, grid, lds, block, s);
+  if (mu) return launch_plan_t<false, true, true, false>(d_args, A, grid, lds, block, s);
+  if (P.occ_lds) return launch_plan_t<false, true, false, false>(d_args, A, grid, lds, block, s);
+  return launch_plan_t<false, false, false, false>(d_args, A, grid, lds, block, s);
 }
 
 }  // namespace tsw

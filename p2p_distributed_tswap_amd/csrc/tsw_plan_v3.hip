@@ -1,9 +1,7 @@
-// tsw_plan_v3.hip — one instantiation of k_plan (tsw_plan_kernel.h): AG=false, OC=false, MUL=false, PG=true.
+// tsw_plan_v3.hip — one instantiation of k_plan (tsw_plan_kernel.h), in a translation unit of its own so that the build
+// compiles the seven in parallel. launch_plan (tsw_plan.hip) says which PlanArgs it serves.
 #include "tsw_plan_kernel.h"
 
 namespace tsw {
-hipError_t launch_plan_v3(const PlanArgs* P, const WorkerArgs& W, uint32_t grid, size_t lds, uint32_t block,
-                          hipStream_t s) {
-  return launch_plan_t<false, false, false, true>(P, W, grid, lds, block, s);
-}
+template hipError_t launch_plan_t<false, false, false, true>(const PlanArgs*, const WorkerArgs&, uint32_t, size_t, uint32_t, hipStream_t);
 }  // namespace tsw

@@ -1,6 +1,6 @@
 """CPU model of k_plan's K4 assignment scan (round 12) against the sequential assignment.
 
-The kernel (tsw_plan_kernel.h, SEC_ASSIGN) takes a step's idle agents in index order in adaptive batches.
+The kernel (tsw_plan_assign.h, sec_assign) takes a step's idle agents in index order in adaptive batches.
 Per batch it bounds every agent's minimum from the chunk boxes of the Morton index (phase A), lets the
 threads that own a chunk within some agent's bound append (chunk, agent mask) to an LDS list of fixed
 capacity, walks the list with one lane per entry (rounds over the list when more chunks pass than fit),

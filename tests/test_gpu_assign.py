@@ -17,7 +17,7 @@ from p2p_distributed_tswap_amd import TSW_EINVAL, Planner, TswapError, maps
 
 pytestmark = pytest.mark.gpu
 
-# tsw_plan_kernel.h: the scan's LDS list of (chunk, agent mask) entries lies in what the step's idle agents leave
+# tsw_plan_assign.h: the scan's LDS list of (chunk, agent mask) entries lies in what the step's idle agents leave
 # free of the 1,024-word `list` (two words an entry), or in SCAN_CAP entries of their own when that is less
 LIST_CAP = 1024
 SCAN_CAP = 64

@@ -408,6 +408,22 @@ def test_mapd_partial_lds_agent_arrays(monkeypatch, mask):
     _plan_vs_oracle(rows, starts, tasks, 30, diag=True)
 
 
+@pytest.mark.parametrize("n,side,part", [(1000, 150, None), (1000, 200, None), (6000, 100, "0")],
+                         ids=["ag_occ", "ag", "occ_mu"])
+def test_mapd_lds_placements(monkeypatch, n, side, part):
+    """The k_plan instantiations that the cases above do not reach, by what fits LDS (choose_plan_lds; run with
+    TSW_PLAN_DEBUG the diagnostic library prints the placement): 1,000 agents on a 150x150 grid — the agent arrays
+    and the occupancy grid but not the movement rounds' MU words beside them, k_plan<AG, OC, !MUL>; on a 200x200
+    grid — the agent arrays alone, k_plan<AG, !OC>; 6,000 agents on a 100x100 grid with no agent array admitted
+    (TSW_PART_LDS=0) — the agent arrays in global memory, OCC and MU (8 B a cell) in LDS, k_plan<!AG, OC, MUL, !PG>
+    (on the 128x128 grid above only OCC fits). Bit-exact against the oracle, 30 steps."""
+    if part is not None:
+        monkeypatch.setenv("TSW_PART_LDS", part)
+    rows = maps.random_map(side, side, 0.1, 0x6002 + side)
+    starts, tasks = maps.make_instance(rows, n, 600, 0x6003)
+    _plan_vs_oracle(rows, starts, tasks, 30, diag=True)
+
+
 def test_mapd_workers_leave_when_idle(monkeypatch):
     """coop workers that all leave (idle timeout cut to 20 us, TSW_WORKER_IDLE_US) while the
     planner still needs pairs: the planner sees `alive == 0`, stops waiting within ~1 ms, the call

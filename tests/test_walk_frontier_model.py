@@ -1,4 +1,4 @@
-"""CPU model of the planner's cached, budgeted step-start walk-ahead (tsw_plan_kernel.h nextnext_prefetch /
+"""CPU model of the planner's cached, budgeted step-start walk-ahead (tsw_plan_walk.h nextnext_prefetch /
 walk_prefetch, round 10).
 
 Per agent the kernel keeps a frontier entry (PlanArgs::wf: the cell the agent stood on at the walk, its goal,
