@@ -1,16 +1,13 @@
 // tsw_astar.h — exact A* next hop (get_path, tswap.rs:288-390) as device functions shared by
-// the K3 kernels (tsw_kernels.hip) and the coop workers inside the plan dispatch (tsw_plan.hip).
+// the K3 kernels (tsw_astar.hip) and the coop workers inside the plan dispatch (tsw_plan.hip).
 // Rust std BinaryHeap semantics restated (push = sift_up; pop = swap last into the root,
 // sift_down_to_bottom, sift_up), ordered by AstarNode::cmp (tswap.rs:314-321). gfx950 only.
 #pragma once
 // The BinaryHeap order (heap_sift_up / heap_pop) and astar_one are __host__ __device__: the host A*
 // service (tsw_host_astar.cpp, plain C++) runs the same functions over the host copy of the grid, so
-// the heap order lives in one place. Everything wave-level below them is device only.
+// the heap order lives in one place (TSW_HD, tsw_internal.h). Everything wave-level below them is device only.
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-#define TSW_HD __host__ __device__ __forceinline__
-#else
-#define TSW_HD inline
 #endif
 
 #include "tsw_internal.h"

@@ -3,7 +3,7 @@
 //
 // What it computes: for goal g, dist[c] = BFS distance from g to every cell c of the
 // 4-connected grid (tswap.rs:44-77 graph), 0xFFFF for blocked/unreachable cells — the same
-// table k_bfs (tsw_kernels.hip) writes; get_path's path length - 1 (tswap.rs:288-390).
+// table k_bfs (tsw_bfs_block.hip) writes; get_path's path length - 1 (tswap.rs:288-390).
 //
 // Why a new kernel: on a den520d-like 256x257 cave a BFS runs ~380 levels but its
 // frontier touches only ~100 of the 2056 row words per level, and a u16 table does not
@@ -83,14 +83,6 @@ __device__ __attribute__((noinline)) void list_put_slow(uint16_t* Ln, uint16_t* 
 
 }  // namespace
 
-// LDS words (u32 units) of one wave; must match the carve in k_bfs_wave. The list area holds
-// at least 17 x 64 u16 (the decode's C table).
-__host__ __device__ __forceinline__ uint32_t wave_bfs_words(uint32_t npw, uint32_t nfk, uint32_t cap) {
-  const uint32_t npw4 = (npw + 3u) & ~3u;
-  const uint32_t ls = cap < 544u ? 544u : cap;
-  return 2u * npw4 + 2u * nfk + ((ls + 3u) & ~3u);
-}
-
 __global__ void __launch_bounds__(1024) k_bfs_wave(WaveBfsArgs A) {
   extern __shared__ __align__(16) uint32_t smem[];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6, nwv = blockDim.x >> 6;
@@ -102,7 +94,7 @@ __global__ void __launch_bounds__(1024) k_bfs_wave(WaveBfsArgs A) {
   uint32_t* WL;
   uint32_t* FL;   // 2 * nfk interleaved flag dwords
   uint16_t* LS;   // 2 * cap list entries (>= 17 x 64 for the decode)
-  {
+  {  // the carve: must match wave_bfs_words (tsw_place.h), which the host's fit test sums
     uint32_t* b = smem + npw4 + wv * wave_bfs_words(npw, nfk, cap);
     V = b;
     WL = b + npw4;
@@ -379,20 +371,6 @@ __global__ void __launch_bounds__(1024) k_bfs_wave(WaveBfsArgs A) {
     atomicAdd((unsigned long long*)&A.prof[2], (unsigned long long)n_lvl);
     atomicAdd((unsigned long long*)&A.prof[3], (unsigned long long)n_chunk);
   }
-}
-
-// flag dwords per buffer: a power of two >= 64 with 32 * K >= npw
-uint32_t bfs_wave_klog(uint32_t npw) {
-  uint32_t kl = 6;
-  while ((32u << kl) < npw) ++kl;
-  return kl;
-}
-
-uint32_t bfs_wave_waves_per_block(uint32_t npw, uint32_t cap, int max_lds) {
-  const size_t per_wave = (size_t)wave_bfs_words(npw, 1u << bfs_wave_klog(npw), cap) * 4u;
-  const size_t shared = (size_t)((npw + 3u) & ~3u) * 4u;
-  if (max_lds <= 0 || shared + per_wave > (size_t)max_lds) return 0;
-  return (uint32_t)std::min<size_t>(16u, ((size_t)max_lds - shared) / per_wave);
 }
 
 hipError_t launch_bfs_wave(const WaveBfsArgs& A0, int max_lds, int num_cu, hipStream_t s) {

@@ -39,8 +39,6 @@ namespace {
 constexpr uint64_t BCOL0 = 0x0101010101010101ull;
 constexpr uint64_t BCOL7 = 0x8080808080808080ull;
 constexpr uint64_t BCB_EVEN = 0xAA55AA55AA55AA55ull;  // cells with (r + c) even
-constexpr uint32_t BIG_THREADS = 512;
-constexpr uint32_t BIG_RT_ROWS = 9;  // decode run table: 17 u16 rows = 9 dword rows per thread
 
 __device__ __forceinline__ uint32_t big_rank(uint64_t m) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -54,27 +52,13 @@ __device__ __forceinline__ uint32_t rt_slot(uint32_t t, uint32_t j, uint32_t bd)
 
 }  // namespace
 
-__host__ __device__ __forceinline__ uint32_t big_bfs_klog(uint32_t nbp) {
-  uint32_t kl = 5;
-  while ((32u << kl) < nbp) ++kl;
-  return kl;
-}
-
-// LDS bytes of one workgroup (must match the carve in k_bfs_big)
-__host__ __device__ __forceinline__ size_t big_bfs_lds(uint32_t nbp, uint32_t cap) {
-  const uint32_t nfk = 1u << big_bfs_klog(nbp);
-  const size_t lists = (size_t)2u * cap * 2u;
-  const size_t rt = (size_t)BIG_RT_ROWS * BIG_THREADS * 4u;  // reuses the flag + list area
-  const size_t tail = (size_t)2u * nfk * 4u + lists;
-  return (size_t)nbp * 8u + (tail > rt ? tail : rt);
-}
-
 __global__ void __launch_bounds__(512) k_bfs_big(BigBfsArgs A) {
   extern __shared__ __align__(16) uint64_t smb[];
   __shared__ uint32_t s_cnt[3], s_gi, s_bad;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, bd = blockDim.x;
   const uint32_t W = A.W, Bp = A.Bp, BW = A.BW, nbp = A.nbp, cap = A.cap, klog = A.klog;
   const uint32_t nfk = 1u << klog, kmask = nfk - 1u;
+  // the carve: must match big_bfs_lds (tsw_place.h), the host's fit test
   uint64_t* V = smb;
   uint32_t* FL = reinterpret_cast<uint32_t*>(smb + nbp);  // 2 * nfk
   uint16_t* LS = reinterpret_cast<uint16_t*>(FL + 2u * nfk);  // 2 * cap
@@ -301,36 +285,20 @@ __global__ void __launch_bounds__(512) k_bfs_big(BigBfsArgs A) {
   }
 }
 
-bool bfs_big_fits(uint32_t nbp, int max_lds, uint32_t* cap_out) {
-  if (nbp > 0xFFFFu || max_lds <= 0) return false;
-  // largest list capacity (<= 8192) whose carve fits
-  for (uint32_t cap = 8192; cap >= 256; cap >>= 1)
-    if (big_bfs_lds(nbp, cap) <= (size_t)max_lds) {
-      if (cap_out) *cap_out = cap;
-      return true;
-    }
-  return false;
-}
-
 hipError_t launch_bfs_big(const BigBfsArgs& A0, int max_lds, int num_cu, hipStream_t s) {
   if (A0.k == 0) return hipSuccess;
   BigBfsArgs A = A0;
   A.klog = big_bfs_klog(A.nbp);
-  A.bp_magic = (uint32_t)((0xFFFFFFFFull + A.Bp) / A.Bp);  // ceil(2^32 / Bp): exact p / Bp for p*Bp < 2^32
+  A.bp_magic = bp_magic(A.Bp);
   const size_t lds = big_bfs_lds(A.nbp, A.cap);
   if (lds > (size_t)max_lds || A.nbp > 0xFFFFu) return hipErrorInvalidValue;
-  const uint32_t per_cu = (uint32_t)std::max<size_t>(1u, (160u * 1024u) / lds);
+  const uint32_t per_cu = (uint32_t)std::max<size_t>(1u, CU_LDS_BYTES / lds);
   const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)num_cu * per_cu, A.k));
   if (grid > A.scratch_wgs) return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute((const void*)k_bfs_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_bfs_big, dim3(grid), dim3(BIG_THREADS), lds, s, A);
   return hipGetLastError();
-}
-
-uint32_t bfs_big_workgroups(uint32_t nbp, uint32_t cap, int num_cu) {
-  const size_t lds = big_bfs_lds(nbp, cap);
-  return (uint32_t)num_cu * (uint32_t)std::max<size_t>(1u, (160u * 1024u) / lds);
 }
 
 }  // namespace tsw

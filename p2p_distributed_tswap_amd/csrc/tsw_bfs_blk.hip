@@ -53,7 +53,6 @@ namespace {
 constexpr uint64_t COL0 = 0x0101010101010101ull;
 constexpr uint64_t COL7 = 0x8080808080808080ull;
 constexpr uint64_t CB_EVEN = 0xAA55AA55AA55AA55ull;  // cells with (r + c) even (row 0 = low byte)
-constexpr uint32_t CT_U16 = 1152;                     // decode run table: 18 rows x 64 lanes u16
 
 __device__ __forceinline__ void lds_sync() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -98,17 +97,6 @@ __device__ __forceinline__ uint32_t ct_slot(uint32_t lane, uint32_t j) {
 
 }  // namespace
 
-// LDS dwords of one wave; must match the carve in k_bfs_blk: V (nbp rounded to even u64), flags,
-// then the list / run-table / staging region LS, 16-B aligned (every part is a multiple of 4 dwords).
-__host__ __device__ __forceinline__ uint32_t blk_bfs_words(uint32_t nbp, uint32_t nfk, uint32_t cap, bool wls) {
-  const uint32_t ls = 2u * cap < CT_U16 ? CT_U16 : 2u * cap;  // u16 entries: two lists, run table, staging
-  return (wls ? 4u : 2u) * ((nbp + 1u) & ~1u) + 2u * nfk + ((ls + 7u) >> 3) * 4u;
-}
-// u64 words of the workgroup's shared part (FR u64 + AB u32), rounded to 16 B
-__host__ __device__ __forceinline__ uint32_t blk_shared_u64(uint32_t nbp) {
-  return (nbp + (nbp + 1u) / 2u + 1u) & ~1u;
-}
-
 // WLS: the west-step blocks WL live in the wave's LDS (after V) instead of global scratch — no
 // memory-side atomics, at the cost of ~nbp*8 more LDS bytes per goal in flight.
 // PAIR (TSW_BFS_PAIR=1, A/B variant): each 32-lane half of a wave runs its own goal (two goals per
@@ -135,7 +123,7 @@ __global__ void __launch_bounds__(1024) k_bfs_blk(BlkBfsArgs A) {
   uint32_t* FL;  // 2 * nfk interleaved flag dwords: block t -> dword t & kmask, bit t >> klog
   uint16_t* LS;  // 2 * cap list entries / decode run table
   uint16_t* CT;  // decode run table (PAIR: the wave's first goal slot's LS; ct_slot separates the halves)
-  {
+  {  // the carve: must match blk_shared_u64 / blk_bfs_words (tsw_place.h), which the host's fit test sums
     uint32_t* b0 = reinterpret_cast<uint32_t*>(smem64 + blk_shared_u64(nbp));
     uint32_t* b = b0 + gs * blk_bfs_words(nbp, nfk, cap, WLS);
     uint32_t* bw = b0 + (PAIR ? 2u * wv : wv) * blk_bfs_words(nbp, nfk, cap, WLS);
@@ -679,24 +667,11 @@ __global__ void __launch_bounds__(1024) k_bfs_blk(BlkBfsArgs A) {
   }
 }
 
-uint32_t bfs_blk_klog(uint32_t nbp) {
-  uint32_t kl = 6;
-  while ((32u << kl) < nbp) ++kl;
-  return kl;
-}
-
-uint32_t bfs_blk_waves_per_block(uint32_t nbp, uint32_t cap, int max_lds, bool wls, bool pair) {
-  const size_t per_wave = (size_t)blk_bfs_words(nbp, 1u << bfs_blk_klog(nbp), cap, wls) * 4u * (pair ? 2u : 1u);
-  const size_t shared = (size_t)blk_shared_u64(nbp) * 8u;  // FR u64 + AB u32
-  if (max_lds <= 0 || shared + per_wave > (size_t)max_lds) return 0;
-  return (uint32_t)std::min<size_t>(16u, ((size_t)max_lds - shared) / per_wave);
-}
-
 hipError_t launch_bfs_blk(const BlkBfsArgs& A0, int max_lds, int num_cu, hipStream_t s) {
   if (A0.k == 0) return hipSuccess;
   BlkBfsArgs A = A0;
   A.klog = bfs_blk_klog(A.nbp);
-  A.bp_magic = (uint32_t)((0xFFFFFFFFull + A.Bp) / A.Bp);  // ceil(2^32 / Bp): exact p / Bp for p*Bp < 2^32
+  A.bp_magic = bp_magic(A.Bp);
   const bool wls = A.wls != 0u, pair = A.pair != 0u;
   const uint32_t gpw = pair ? 2u : 1u;  // goal slots per wave
   const size_t per_wave = (size_t)blk_bfs_words(A.nbp, 1u << A.klog, A.cap, wls) * 4u * gpw;

@@ -68,21 +68,11 @@ __device__ __forceinline__ uint64_t rs_mask(const uint64_t* FR, uint32_t p, uint
 
 }  // namespace
 
-// LDS bytes of k_bfs_mg for a grid (0 if the layout's indices overflow)
-__host__ __device__ __forceinline__ uint32_t mg_vbytes(uint32_t W, uint32_t H) {
-  return (((W + 2u) * (H + 2u) * 2u) + 15u) & ~15u;
-}
-__host__ __device__ __forceinline__ uint32_t mg_nwc(uint32_t nbp) { return ((nbp + 31u) / 32u + 3u) & ~3u; }
-
-size_t bfs_mg_lds_bytes(uint32_t W, uint32_t H, uint32_t nbp) {
-  return (size_t)mg_vbytes(W, H) + (size_t)nbp * 8u + (size_t)nbp * 4u + 3u * mg_nwc(nbp) * 4u +
-         (((size_t)nbp * 2u + 15u) & ~(size_t)15u);
-}
-
 __global__ void __launch_bounds__(1024) k_bfs_mg(MgBfsArgs A) {
   extern __shared__ __align__(16) uint8_t smem[];
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6, nwv = blockDim.x >> 6, bd = blockDim.x;
   const uint32_t W = A.W, H = A.H, Wp = W + 2u, Bp = A.Bp, nbp = A.nbp, nwc = mg_nwc(nbp);
+  // the carve: must match bfs_mg_lds_bytes (tsw_place.h), the host's fit test
   uint16_t* V = reinterpret_cast<uint16_t*>(smem);
   uint64_t* FR = reinterpret_cast<uint64_t*>(smem + mg_vbytes(W, H));
   uint32_t* AB = reinterpret_cast<uint32_t*>(FR + nbp);
@@ -327,6 +317,8 @@ __global__ void __launch_bounds__(1024) k_bfs_mg(MgBfsArgs A) {
   }
 }
 
+bool bfs_mg_built() { return true; }
+
 hipError_t launch_bfs_mg(const MgBfsArgs& A, int max_lds, int num_cu, hipStream_t s) {
   if (A.ngroups == 0) return hipSuccess;
   const size_t lds = bfs_mg_lds_bytes(A.W, A.H, A.nbp);
@@ -341,7 +333,7 @@ hipError_t launch_bfs_mg(const MgBfsArgs& A, int max_lds, int num_cu, hipStream_
 
 #else   // production build: no k_bfs_mg (TSW_BFS_KERNEL is a diagnostic knob)
 
-size_t bfs_mg_lds_bytes(uint32_t, uint32_t, uint32_t) { return ~(size_t)0; }
+bool bfs_mg_built() { return false; }
 
 hipError_t launch_bfs_mg(const MgBfsArgs&, int, int, hipStream_t) { return hipErrorInvalidValue; }
 

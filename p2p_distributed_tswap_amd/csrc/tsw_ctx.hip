@@ -255,7 +255,7 @@ tsw_ctx* tsw_create(const uint8_t* cells, uint32_t w, uint32_t h, const tsw_opts
   {
     // k_bfs_wave layout: word (r, cw) at (r + 1) * Wp + cw, zero guard column and rows
     c->Wp = Ww + 1u;
-    c->npw = (h + 2u) * c->Wp;
+    c->npw = bfs_wave_npw(w, h);  // (h + 2) * Wp
     std::vector<uint32_t> frp(c->npw, 0u);
     for (uint32_t y = 0; y < h; ++y)
       for (uint32_t cw = 0; cw < Ww; ++cw) frp[(size_t)(y + 1u) * c->Wp + cw] = fb[(size_t)y * Ww + cw];
@@ -264,7 +264,7 @@ tsw_ctx* tsw_create(const uint8_t* cells, uint32_t w, uint32_t h, const tsw_opts
     c->BW = (w + 7u) / 8u;
     c->BH = (h + 7u) / 8u;
     c->Bp = c->BW + 1u;
-    c->nbp = (c->BH + 2u) * c->Bp;
+    c->nbp = bfs_blk_nbp(w, h);  // (BH + 2) * Bp
     std::vector<uint64_t> frb(c->nbp, 0ull);
     for (uint32_t y = 0; y < h; ++y)
       for (uint32_t x = 0; x < w; ++x)

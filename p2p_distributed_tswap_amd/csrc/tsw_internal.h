@@ -28,6 +28,15 @@
 #define TSW_DIAG_BITS(x) 0u
 #endif
 
+// Functions that device code and plain host C++ share: the LDS carve sizes of tsw_place.h (a kernel's
+// carve and the host's fit test) and the A* heap order of tsw_astar.h (the K3 kernels and the host A*
+// service). Under hipcc the including file has <hip/hip_runtime.h> before the first use.
+#if defined(__HIPCC__)
+#define TSW_HD __host__ __device__ __forceinline__
+#else
+#define TSW_HD inline
+#endif
+
 namespace tsw {
 
 constexpr uint8_t NH_STAY = 4;

@@ -1,4 +1,6 @@
-// tsw_launch.h — host-callable launch wrappers for the kernels in tsw_kernels.hip.
+// tsw_launch.h — host-callable launch wrappers of the K1 (tsw_bfs*.hip), classification (tsw_classify.hip), K3
+// (tsw_astar.hip), code-store (tsw_codes.hip), decision (tsw_decide.hip) and probe kernels, with the K1 argument
+// structs. What fits where, and which kernel a launch takes, is tsw_place.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -6,10 +8,9 @@
 #include <cstddef>
 
 #include "tsw_internal.h"
+#include "tsw_place.h"
 
 namespace tsw {
-
-size_t bfs_lds_bytes(const DevGrid& G, bool lds_table);
 
 hipError_t launch_bfs(const DevGrid& G, const uint32_t* goals, const uint32_t* slots, uint32_t k,
                       uint16_t* dist_base, uint64_t dstride, uint8_t* nh_base, uint64_t nstride,
@@ -35,8 +36,6 @@ struct WaveBfsArgs {
   uint64_t scratch_waves; // waves the scratch buffers are sized for
   uint64_t* prof;         // optional: [bfs cycles, decode cycles, levels, chunks] summed over waves
 };
-// waves per workgroup that fit max_lds (0: the kernel does not fit this grid)
-uint32_t bfs_wave_waves_per_block(uint32_t npw, uint32_t cap, int max_lds);
 hipError_t launch_bfs_wave(const WaveBfsArgs& A, int max_lds, int num_cu, hipStream_t s);
 
 // K1 v3 (tsw_bfs_blk.hip): one wavefront per goal over 8x8 cell blocks. Block (bx, by) sits at
@@ -67,8 +66,6 @@ struct BlkBfsArgs {
   uint32_t wls;           // west-step blocks in LDS (k_bfs_blk<true, *>) instead of global scratch
   uint32_t pair;          // two goals per wave, one per 32-lane half (k_bfs_blk<*, true>)
 };
-// waves per workgroup that fit LDS (pair: two goal slots per wave)
-uint32_t bfs_blk_waves_per_block(uint32_t nbp, uint32_t cap, int max_lds, bool wls, bool pair);
 hipError_t launch_bfs_blk(const BlkBfsArgs& A, int max_lds, int num_cu, hipStream_t s);
 
 // K1 v4 (tsw_bfs_big.hip): one WORKGROUP per goal over 8x8 cell blocks, free blocks and run
@@ -92,8 +89,6 @@ struct BigBfsArgs {
   uint32_t vec16;
   uint32_t scratch_wgs;   // workgroups the scratch buffers are sized for
 };
-bool bfs_big_fits(uint32_t nbp, int max_lds, uint32_t* cap_out);
-uint32_t bfs_big_workgroups(uint32_t nbp, uint32_t cap, int num_cu);
 hipError_t launch_bfs_big(const BigBfsArgs& A, int max_lds, int num_cu, hipStream_t s);
 
 // K1 v5 (tsw_bfs_mg.hip): one WORKGROUP per group of <= 16 same-parity goals, a u16 goal mask per
@@ -117,7 +112,7 @@ struct MgBfsArgs {
   uint32_t scratch_wgs;   // workgroups the scratch buffers are sized for
   uint64_t* prof;         // optional: [bfs cycles, decode cycles, levels] summed over groups
 };
-size_t bfs_mg_lds_bytes(uint32_t W, uint32_t H, uint32_t nbp);
+bool bfs_mg_built();  // the library holds k_bfs_mg (the diagnostic build)
 hipError_t launch_bfs_mg(const MgBfsArgs& A, int max_lds, int num_cu, hipStream_t s);
 
 hipError_t launch_classify(const DevGrid& G, const uint32_t* goals, const uint32_t* slots, uint32_t k,
@@ -132,8 +127,7 @@ hipError_t launch_astar(const DevGrid& G, const AstarQuery* Q, const uint32_t* n
                         int32_t* lens, uint64_t* heaps, uint32_t hcap, uint32_t* gs_all, uint32_t* epochs,
                         uint32_t nslots, uint32_t* err, hipStream_t s);
 
-// LDS-heap A* for grids of <= 1024 cells; queries whose heap outgrows LDS land in ovf.
-bool astar_lds_ok(const DevGrid& G);
+// LDS-heap A* for grids of <= 1024 cells (astar_lds_ok); queries whose heap outgrows LDS land in ovf.
 hipError_t launch_astar_lds(const DevGrid& G, const AstarQuery* Q, uint32_t nq, uint8_t* nh_base, uint64_t nstride,
                             uint8_t* res, int32_t* lens, uint16_t* gs16, uint32_t* epochs, uint32_t nslots,
                             AstarQuery* ovf, uint32_t* novf, uint32_t* qnext, hipStream_t s);
@@ -141,9 +135,7 @@ hipError_t launch_astar_lds(const DevGrid& G, const AstarQuery* Q, uint32_t nq, 
 // One query per wave, LDS heap (grids of > 1024 cells); gs_all/epochs: nslots u32 g_score
 // arrays of ncell words (used only when the grid's g_scores do not fit LDS).
 // global_gs: keep the g_scores in the global slots even when the grid's fit LDS (second tier
-// for queries whose byte-encoded g_scores overflowed).
-uint32_t astar_wave_slots(const DevGrid& G, int num_cu, bool global_gs = false);
-bool astar_wave_lds_gs(const DevGrid& G);  // k_astar_wave keeps this grid's g_scores in LDS
+// for queries whose byte-encoded g_scores overflowed). Slots and sizes: astar_wave_slots, tsw_place.h.
 // diagnostics of k_astar_wave (read once per context from the environment, tsw_ctx.h Tunables)
 constexpr uint32_t ASTAR_DIAG_SERIAL = 1u;  // lone-lane heap core instead of the wave-cooperative one
 constexpr uint32_t ASTAR_DIAG_PROF = 2u;    // per-query pop / clock profile printed to stderr

@@ -16,6 +16,8 @@
 #define TSW_RING_HD inline
 #endif
 
+#include "tsw_place.h"
+
 namespace tsw {
 
 // ---- host A* service: request words (PlanArgs::hreq / hrep / hask) ----------------------------
@@ -320,17 +322,7 @@ struct PlanArgs {
   uint32_t walk_step;
 };
 
-// Agent arrays that go to LDS one by one when all of them do not fit (PlanArgs::part_lds), in the
-// order the host admits them: the rules phase's successor chains and labels first (its relabel walks
-// and firing scans are serial dependent loads), then cells and goals, then the code caches.
-enum : uint32_t {
-  PART_SUCC = 1u, PART_ONC = 2u, PART_V = 4u, PART_G = 8u, PART_NHC = 16u, PART_CANDC = 32u, PART_GT = 64u,
-  PART_PG = 0x3Fu,  // the subset k_plan<false, *, *, true> carves unconditionally (LDS-typed accesses)
-};
-size_t part_lds_bytes(uint32_t n, uint32_t part);
-// flinks: the pointer-doubling buffers F1/F2 alone in LDS (when the agent arrays are not)
-size_t plan_lds_bytes(uint32_t n, uint32_t ncell, uint32_t m, bool agents, bool occ, bool tasks, bool flinks = false,
-                      bool mu = true, uint32_t part = 0u);
+// The PART_* bits of part_lds and the placement's byte formulas (part_lds_bytes, plan_lds_bytes): tsw_place.h.
 hipError_t launch_occ(const uint32_t* v, uint32_t n, uint32_t* occ, uint32_t* cnt, uint32_t ncell, uint32_t* dups,
                       hipStream_t s);
 // Coop-mode K3 workers (tsw_worker.h) run in the workgroups 1.. of the plan dispatch: claim queued
@@ -382,16 +374,7 @@ struct WorkerArgs {
   uint32_t slow_mask, slow_mult;  // idle workers with (wid & slow_mask) != 0 poll slow_mult times less often
   unsigned long long idle_ticks;  // a worker idle this long (100 MHz ticks) exits (5 s)
 };
-// Worker placement: per-wave LDS (heap, g-scores, free bitmap) sets the waves per CU. g-scores stay
-// in LDS (fastest per pop) unless that leaves < 3 waves per CU while many agents can need queries at
-// once (n > 2000): then they move to the global slots and more waves run.
-struct WorkerCfg {
-  uint32_t gs_lds, stage_fb, hcap, waves;
-  uint32_t dag;  // WorkerArgs::dag
-  size_t lds;
-};
-WorkerCfg worker_config(const DevGrid& G, int num_cu, uint32_t n_agents, uint32_t hcap_want, int force_gs = -1,
-                        bool dag_exit = true, size_t lds_cap = 160u * 1024u, int force_fb = -1);
+// Worker placement (WorkerCfg, worker_config, worker_layout): tsw_place.h.
 
 // The plan dispatch: workgroup 0 runs k_plan's planner (block threads, lds bytes of dynamic LDS);
 // with W (coop mode) workgroups 1..worker_blocks run W->wpb K3 worker waves each.

@@ -70,31 +70,12 @@ static T* per_agent(tsw_ctx* c, DevBuf<T>& b, uint32_t n, int fill) {
   return b.p && hipMemsetAsync(b.p, fill, (size_t)n * sizeof(T), c->s) == hipSuccess ? b.p : nullptr;
 }
 
-// What of the planner's state lives in LDS, in priority order: agents, occupancy grid, task table.
-static void choose_plan_lds(const tsw_ctx* c, PlanArgs* Pp) {
-  PlanArgs& P = *Pp;
-  const size_t budget = (size_t)std::max(c->max_lds - 2048, 0);
-  bool ag = plan_lds_bytes(P.n, P.ncell, P.m, true, false, false) <= budget;
-  // without the whole set, single agent arrays in priority order (PART_*: the rules phase's serial
-  // successor walks and firing scans read SUCC / ONC / V / G; wh10k rules 3.9 -> ? s), then the rules
-  // relabel's pointer-doubling buffers
-  uint32_t part = 0;
-  if (!ag)
-    for (uint32_t bit : {PART_SUCC, PART_ONC, PART_V, PART_G, PART_NHC, PART_CANDC, PART_GT})
-      if ((c->tun.part_lds & bit) && plan_lds_bytes(P.n, P.ncell, P.m, false, false, false, false, true, part | bit) <= budget)
-        part |= bit;
-  bool fl = !ag && c->tun.flinks_lds && plan_lds_bytes(P.n, P.ncell, P.m, false, false, false, true, true, part) <= budget;
-  // the occupancy grid with the movement rounds' MU words, else OCC alone (every rules round reads
-  // OCC: C3's 170x84 fits OCC but not MU beside the agent arrays)
-  bool mu = P.n < 65535u && plan_lds_bytes(P.n, P.ncell, P.m, ag, true, false, fl, true, part) <= budget;  // MU32: 16-bit agent ids
-  bool oc = mu || (c->tun.occ_split && plan_lds_bytes(P.n, P.ncell, P.m, ag, true, false, fl, false, part) <= budget);
-  const bool tk = false;  // K4 reads its spatial index from global memory (the chunks it needs only)
-  P.part_lds = part;
-  P.f_lds = fl;
-  P.mu_lds = mu;
-  P.agents_lds = ag;
-  P.occ_lds = oc;
-  P.tasks_lds = tk;
+// What of the planner's state lives in LDS (choose_plan_placement, tsw_place.h), into PlanArgs.
+static void choose_plan_lds(const tsw_ctx* c, PlanArgs* P) {
+  const PlanPlacement pl =
+      choose_plan_placement(P->n, P->ncell, P->m, c->max_lds, c->tun.part_lds, c->tun.flinks_lds, c->tun.occ_split);
+  P->part_lds = pl.part, P->f_lds = pl.flinks, P->mu_lds = pl.mu;
+  P->agents_lds = pl.agents, P->occ_lds = pl.occ, P->tasks_lds = pl.tasks;
 }
 
 static PlanArgs plan_args(tsw_ctx* c, uint32_t n, uint32_t m, uint32_t mode, bool want_goals) {
@@ -314,19 +295,17 @@ static int worker_args(tsw_ctx* c, PlanArgs& P, size_t lds, uint32_t block, Work
   W.gs_lds = wcfg.gs_lds;
   W.stage_fb = wcfg.stage_fb;
   W.hcap = wcfg.hcap;
-  // one dispatch: the planner (workgroup 0) and one worker workgroup on every other CU, each holding
-  // as many single-wave workers as its dynamic LDS (the planner's, whole-CU size) carves
-  W.lds_per_wave = (uint32_t)((wcfg.lds + 15u) & ~(size_t)15u);
-  W.wpb = W.lds_per_wave ? (uint32_t)std::min<size_t>(block / 64u, lds / W.lds_per_wave) : 0u;
-  const uint32_t want = W.wpb * (uint32_t)std::max(c->num_cu - 1, 0);
-  TRY(ensure_astar_scratch(c, want));  // one g-score / heap slot per worker wave
+  const WorkerLayout L = worker_layout(wcfg.lds, lds, block, c->num_cu);
+  TRY(ensure_astar_scratch(c, L.want));  // one g-score / heap slot per worker wave
+  W.lds_per_wave = L.lds_per_wave;
+  W.wpb = L.wpb;
   W.gs_all = c->d_gs;
   W.epochs = c->d_epochs;
   W.heaps = c->d_heaps;
   W.ghcap = c->hcap;
-  W.nworkers = std::min(want, c->nslots);
+  W.nworkers = L.nworkers(c->nslots);
   P.spec_hi = 2u * W.nworkers;  // a backlog of two pairs per worker counts as keeping up
-  *wblocks = W.wpb ? (W.nworkers + W.wpb - 1u) / W.wpb : 0u;
+  *wblocks = L.wblocks(c->nslots);
   if (c->tun.plan_debug)
     fprintf(stderr, "[k_plan] workers: %u waves (%u per workgroup), g-scores %u, heap %u entries, DAG exit %u, %u B LDS each\n",
             W.nworkers, W.wpb, wcfg.gs_lds, wcfg.hcap, wcfg.dag, W.lds_per_wave);
@@ -362,7 +341,7 @@ static int setup_dispatch(tsw_ctx* c, PlanArgs& P, Dispatch* D) {
   const size_t planner = plan_lds_bytes(P.n, P.ncell, P.m, P.agents_lds, P.occ_lds, P.tasks_lds, P.f_lds, P.mu_lds, P.part_lds);
   // coop mode: the planner block reserves its CU's whole LDS so no worker wave is placed beside it
   // (they would compete for its SIMDs and LDS bandwidth on the critical path)
-  D->lds = P.coop ? std::max<size_t>(planner, (size_t)std::max(c->max_lds - 2048, 0)) : planner;
+  D->lds = P.coop ? std::max<size_t>(planner, (size_t)std::max(c->max_lds - PLAN_LDS_RESERVE, 0)) : planner;
   // one lane per agent in the parallel passes when possible; >= 4 waves for the task argmin
   D->block = std::min<uint32_t>(PLAN_BLOCK_MAX, std::max<uint32_t>(256, (P.n + 63) / 64 * 64));
   if (c->tun.plan_block) D->block = std::max<uint32_t>(64u, c->tun.plan_block);

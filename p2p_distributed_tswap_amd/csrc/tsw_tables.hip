@@ -1,6 +1,7 @@
 // tsw_tables.hip — K1 orchestration and the goal-table store of the host runtime (tsw_ctx.h): the K1
-// launch orders and kernel choice (run_bfs), the store's slots with their LRU eviction, the table builds
-// (ensure_tables) and the table entry points of include/tswap.h. Host code only.
+// launch orders and launches (run_bfs; the kernel choice is choose_bfs, tsw_place.h), the store's slots
+// with their LRU eviction, the table builds (ensure_tables) and the table entry points of
+// include/tswap.h. Host code only.
 #include "tsw_ctx.h"
 
 namespace tsw {
@@ -28,19 +29,17 @@ static int ensure_ktmp(tsw_ctx* c, size_t want, size_t* batch) {
   return TSW_OK;
 }
 
-// K1 launch order: longest BFS first. A goal's level count is its eccentricity; the distance
-// to the farthest grid corner bounds it and ranks goals well enough that the work queue's last
-// wave of goals is the short ones (LPT scheduling) instead of a few long ones running on an
-// otherwise idle chip. Output positions are carried in `slots`. TSW_BFS_ORDER=0 keeps the
-// caller's order (A/B).
-// k_bfs_mg serves this launch: selected explicitly (TSW_BFS_KERNEL=mg, diagnostic build — measured
-// 5.5 ms vs k_bfs_blk's 2.7 ms on den520d's 10k goals), its LDS layout fits and the
-// levels fit u16 (<= 65535 free cells)
-static bool mg_selected(const tsw_ctx* c, size_t k) {
-  (void)k;
-  if (c->tun.bfs_mode != 5u) return false;
-  if (c->nfree > 0xFFFFu || c->nbp > 0xFFFFu || c->max_lds <= 0) return false;
-  return bfs_mg_lds_bytes(c->G.W, c->G.H, c->nbp) <= (size_t)c->max_lds;
+// The K1 kernel of this context's grid and knobs (choose_bfs, tsw_place.h): bfs_lpt_order and run_bfs
+// both ask here, so the launch order and the launch cannot disagree.
+static BfsChoice bfs_choice(const tsw_ctx* c) {
+  const BfsGeom g{c->G.W, c->G.H, c->G.ncell, c->nfree, c->npw, c->nbp};
+  const BfsKnobs t{c->tun.bfs_mode, c->tun.blk_cap, c->tun.bfs_cap, c->tun.bfs_waves, c->tun.bfs_wls, c->tun.bfs_pair};
+  return choose_bfs(g, t, c->max_lds, c->num_cu, bfs_mg_built());
+}
+
+static bool mg_selected(const tsw_ctx* c) {
+  const BfsChoice ch = bfs_choice(c);
+  return ch.kernel == BFS_MG && ch.fits;
 }
 
 // k_bfs_mg launch order: goals grouped by (cell parity, Morton order) into groups of <= 16 (one
@@ -85,9 +84,14 @@ static void bfs_mg_order(tsw_ctx* c, std::vector<uint32_t>& goals, std::vector<u
   slots.swap(s2);
 }
 
+// K1 launch order: longest BFS first. A goal's level count is its eccentricity; the distance
+// to the farthest grid corner bounds it and ranks goals well enough that the work queue's last
+// wave of goals is the short ones (LPT scheduling) instead of a few long ones running on an
+// otherwise idle chip. Output positions are carried in `slots`. TSW_BFS_ORDER=0 keeps the
+// caller's order (A/B). When k_bfs_mg serves the launch, its grouped order instead (bfs_mg_order).
 static void bfs_lpt_order(tsw_ctx* c, std::vector<uint32_t>& goals, std::vector<uint32_t>& slots) {
   c->h_mg_grp.clear();
-  if (mg_selected(c, goals.size())) {
+  if (mg_selected(c)) {
     bfs_mg_order(c, goals, slots);
     return;
   }
@@ -116,9 +120,6 @@ static void bfs_lpt_order(tsw_ctx* c, std::vector<uint32_t>& goals, std::vector<
   slots.swap(s2);
 }
 
-// K1 over k goals (device arrays; slots may be null = goal index): the wave-per-goal kernel
-// when its LDS fits, else the workgroup-per-goal kernel. Next-hop codes (nh != null) come
-// fused from k_bfs, or from k_classify over the finished tables after k_bfs_wave.
 // per-wave scratch of the wave-per-goal kernels: `words` u16 anchors + `lwords` u16 list overflow
 static int ensure_wave_scratch(tsw_ctx* c, uint64_t want, size_t words, size_t lwords) {
   if (want <= c->wave_scratch && words <= c->scratch_words && lwords <= c->scratch_lwords) return TSW_OK;
@@ -165,191 +166,207 @@ static int bfs_prof_print(tsw_ctx* c, const char* name, uint32_t k) {
   return TSW_OK;
 }
 
-// K1 over k goals (device arrays; slots may be null = goal index): the 8x8-block wave-per-goal
-// kernel when its LDS fits, else the row-word wave-per-goal kernel, else the workgroup-per-goal
-// kernel. Next-hop codes (nh != null) come fused from k_bfs, or from k_classify over the
-// finished tables after the wave kernels.
-static int run_bfs(tsw_ctx* c, const uint32_t* goals, const uint32_t* slots, uint32_t k, uint16_t* dist, uint64_t dstride,
-            uint8_t* nh, uint8_t* govf = nullptr) {
-  if (k == 0) return TSW_OK;
-  const bool vec16 = c->G.W % 8u == 0u && dstride % 8u == 0u && ((uintptr_t)dist & 15u) == 0u;
-  const uint32_t max_waves = c->tun.bfs_waves;
-  const uint32_t bfs_mode = c->tun.bfs_mode;
-  if (mg_selected(c, k) && !c->h_mg_grp.empty() && c->h_mg_grp.back() == k) {
-    // goal-bit-parallel groups (the launch order came from bfs_mg_order)
-    Timer t(c, CAT_BFS);
-    const uint32_t ngroups = (uint32_t)c->h_mg_grp.size() - 1u;
-    const uint32_t wlw = (c->G.ncell + 1u) / 2u;
-    const uint32_t wgs = (uint32_t)std::max(c->num_cu, 1);
-    if (c->mg_wgs < wgs || !c->d_mg_wl) {
-      HIPCHK(hipStreamSynchronize(c->s));
-      c->mg_wgs = 0;
-      HIPCHK(c->d_mg_wl.reset());
-      HIPCHK(c->d_mg_anch.reset());
-      HIPCHK(c->d_mg_wl.alloc((size_t)wgs * wlw));
-      HIPCHK(c->d_mg_anch.alloc((size_t)wgs * std::max<uint32_t>(c->nrs, 1u) * 16u));
-      c->mg_wgs = wgs;
-    }
-    TRY(grow_synced(c, c->d_mg_grp, c->h_mg_grp.size()));
-    HIPCHK(hipMemcpyAsync(c->d_mg_grp, c->h_mg_grp.data(), c->h_mg_grp.size() * 4u, hipMemcpyHostToDevice, c->s));
-    MgBfsArgs A{};
-    A.W = c->G.W;
-    A.H = c->G.H;
-    A.Bp = c->Bp;
-    A.nbp = c->nbp;
-    A.bp_magic = (uint32_t)((0xFFFFFFFFull + c->Bp) / c->Bp);
-    A.frb = c->d_frb;
-    A.abase = c->d_abase;
-    A.nrs = std::max<uint32_t>(c->nrs, 1u);
-    A.goals = goals;
-    A.slots = slots;
-    A.grp = c->d_mg_grp;
-    A.ngroups = ngroups;
-    A.dist = dist;
-    A.dstride = dstride;
-    A.wl = c->d_mg_wl;
-    A.wlw = wlw;
-    A.anch = c->d_mg_anch;
-    A.work = &c->d_stat->work;
-    A.err = &c->d_stat->err;
-    A.scratch_wgs = c->mg_wgs;
-    A.prof = (uint64_t*)bfs_prof_buf(c);
-    HIPCHK(hipMemsetAsync(&c->d_stat->work, 0, 4, c->s));
-    HIPCHK(launch_bfs_mg(A, c->max_lds, c->num_cu, c->s));
-    // the host copy of the group offsets must outlive the async upload
+// What every K1 rung is given, and fills into its kernel's argument struct the same way.
+struct BfsJob {
+  const uint32_t* goals;
+  const uint32_t* slots;
+  uint32_t k;
+  uint16_t* dist;
+  uint64_t dstride;
+  uint8_t* nh;
+  uint8_t* govf;
+  uint32_t vec16;
+  uint32_t* work;
+  uint32_t* err;
+  uint64_t* prof;  // set by bfs_begin
+};
+
+template <class Args>
+static void bfs_fill(Args& A, const BfsJob& J) {  // what all four argument structs hold
+  A.goals = J.goals;
+  A.slots = J.slots;
+  A.dist = J.dist;
+  A.dstride = J.dstride;
+  A.work = J.work;
+  A.err = J.err;
+}
+template <class Args>
+static void bfs_fill_goals(Args& A, const BfsJob& J) {  // ... and the goal-per-wave / -workgroup ones
+  bfs_fill(A, J);
+  A.k = J.k;
+  A.govf = J.govf;
+  A.vec16 = J.vec16;
+}
+
+// before a rung's launch: the profile buffer (the kernels that fill one) and the work counter zeroed
+static int bfs_begin(tsw_ctx* c, BfsJob& J, bool prof) {
+  J.prof = prof ? (uint64_t*)bfs_prof_buf(c) : nullptr;
+  HIPCHK(hipMemsetAsync(J.work, 0, 4, c->s));
+  return TSW_OK;
+}
+
+// after it: the profile print, and the next-hop codes from k_classify over the finished tables
+static int bfs_finish(tsw_ctx* c, const BfsJob& J, const char* name) {
+  if (J.prof) TRY(bfs_prof_print(c, name, J.k));
+  if (J.nh) HIPCHK(launch_classify(c->G, J.goals, J.slots, J.k, J.dist, J.dstride, J.nh, c->s));
+  return TSW_OK;
+}
+
+// goal-bit-parallel groups (the launch order came from bfs_mg_order)
+static int run_bfs_mg(tsw_ctx* c, BfsJob& J) {
+  const uint32_t ngroups = (uint32_t)c->h_mg_grp.size() - 1u;
+  const uint32_t wlw = (c->G.ncell + 1u) / 2u;
+  const uint32_t wgs = (uint32_t)std::max(c->num_cu, 1);
+  if (c->mg_wgs < wgs || !c->d_mg_wl) {
     HIPCHK(hipStreamSynchronize(c->s));
-    if (A.prof) TRY(bfs_prof_print(c, "k_bfs_mg", k));
-    if (nh) HIPCHK(launch_classify(c->G, goals, slots, k, dist, dstride, nh, c->s));
-    return TSW_OK;
+    c->mg_wgs = 0;
+    HIPCHK(c->d_mg_wl.reset());
+    HIPCHK(c->d_mg_anch.reset());
+    HIPCHK(c->d_mg_wl.alloc((size_t)wgs * wlw));
+    HIPCHK(c->d_mg_anch.alloc((size_t)wgs * std::max<uint32_t>(c->nrs, 1u) * 16u));
+    c->mg_wgs = wgs;
   }
-  if (bfs_mode == 5) RET(TSW_EINVAL, "k_bfs_mg does not fit this grid (forced kernel mg)");
-  uint32_t nbw = 0;
-  // two goals per wave only where two goal slots per wave fit LDS, else one
-  bool pair = c->tun.bfs_pair != 0u;
-  if ((bfs_mode == 0 || bfs_mode == 3) && c->nbp <= 0x10000u) {
-    nbw = std::min(max_waves, bfs_blk_waves_per_block(c->nbp, c->tun.blk_cap, c->max_lds, c->tun.bfs_wls != 0u, pair));
-    if (nbw == 0 && pair) {
-      pair = false;
-      nbw = std::min(max_waves, bfs_blk_waves_per_block(c->nbp, c->tun.blk_cap, c->max_lds, c->tun.bfs_wls != 0u, false));
-    }
-  }
-  if (nbw == 0 && bfs_mode == 3) RET(TSW_EINVAL, "k_bfs_blk does not fit this grid (forced kernel blk)");
-  if (nbw > 0) {
-    Timer t(c, CAT_BFS);
-    // scratch per goal slot: one per wave, two with TSW_BFS_PAIR
-    TRY(ensure_wave_scratch(c, (uint64_t)c->num_cu * nbw * (pair ? 2u : 1u), std::max<size_t>(c->nrs, 1),
-                            (size_t)c->nbp * 2u));
-    TRY(ensure_wlg(c));
-    BlkBfsArgs A{};
-    A.W = c->G.W;
-    A.H = c->G.H;
-    A.BW = c->BW;
-    A.BH = c->BH;
-    A.Bp = c->Bp;
-    A.nbp = c->nbp;
-    A.cap = c->tun.blk_cap;
-    A.frb = c->d_frb;
-    A.abase = c->d_abase;
-    A.nrs = c->nrs;
-    A.goals = goals;
-    A.slots = slots;
-    A.k = k;
-    A.dist = dist;
-    A.dstride = dstride;
-    A.anch = c->d_anch;
-    A.lovf = c->d_lovf;
-    A.wlg = c->d_wlg;
-    A.work = &c->d_stat->work;
-    A.err = &c->d_stat->err;
-    A.govf = govf;
-    A.vec16 = vec16 ? 1u : 0u;
-    A.stage = (dstride % 8u == 0u && ((uintptr_t)dist & 15u) == 0u && !c->tun.bfs_nostage) ? 1u : 0u;
-    A.dbg = c->tun.bfs_dbg;
-    A.wls = c->tun.bfs_wls;
-    A.pair = pair ? 1u : 0u;
-    A.max_waves = nbw;
-    A.scratch_waves = std::min(c->wave_scratch, c->wlg_waves);
-    A.prof = (uint64_t*)bfs_prof_buf(c);
-    HIPCHK(hipMemsetAsync(&c->d_stat->work, 0, 4, c->s));
-    HIPCHK(launch_bfs_blk(A, c->max_lds, c->num_cu, c->s));
-    if (A.prof) TRY(bfs_prof_print(c, "k_bfs_blk", k));
-    if (nh) HIPCHK(launch_classify(c->G, goals, slots, k, dist, dstride, nh, c->s));
-    return TSW_OK;
-  }
-  uint32_t nwv = 0;
-  if ((bfs_mode == 0 || bfs_mode == 1) && c->npw <= 0x8000u)
-    nwv = bfs_wave_waves_per_block(c->npw, c->tun.bfs_cap, c->max_lds);
-  if (nwv == 0 && bfs_mode == 1) RET(TSW_EINVAL, "k_bfs_wave does not fit this grid (forced kernel wave)");
-  uint32_t big_cap = 0;
-  if (nwv == 0 && (bfs_mode == 0 || bfs_mode == 4) && bfs_big_fits(c->nbp, c->max_lds, &big_cap)) {
-    // large grids (e.g. 1024x1024): one workgroup per goal, shared visited bitmap in LDS
-    Timer t(c, CAT_BFS);
-    const uint32_t nwg = bfs_big_workgroups(c->nbp, big_cap, c->num_cu);
-    TRY(ensure_wave_scratch(c, nwg, std::max<size_t>(c->nrs, 1), (size_t)c->nbp * 2u));
-    TRY(ensure_wlg(c));
-    BigBfsArgs A{};
-    A.W = c->G.W;
-    A.H = c->G.H;
-    A.BW = c->BW;
-    A.BH = c->BH;
-    A.Bp = c->Bp;
-    A.nbp = c->nbp;
-    A.cap = big_cap;
-    A.frb = c->d_frb;
-    A.abase = c->d_abase;
-    A.goals = goals;
-    A.slots = slots;
-    A.k = k;
-    A.dist = dist;
-    A.dstride = dstride;
-    A.nrs = std::max<uint32_t>(c->nrs, 1u);
-    A.anch = c->d_anch;
-    A.lovf = c->d_lovf;
-    A.wlg = reinterpret_cast<uint64_t*>(c->d_wlg.p);
-    A.work = &c->d_stat->work;
-    A.err = &c->d_stat->err;
-    A.govf = govf;
-    A.vec16 = vec16 ? 1u : 0u;
-    A.scratch_wgs = (uint32_t)std::min<uint64_t>(c->wave_scratch, c->wlg_waves);
-    HIPCHK(hipMemsetAsync(&c->d_stat->work, 0, 4, c->s));
-    HIPCHK(launch_bfs_big(A, c->max_lds, c->num_cu, c->s));
-    if (nh) HIPCHK(launch_classify(c->G, goals, slots, k, dist, dstride, nh, c->s));
-    return TSW_OK;
-  }
-  if (bfs_mode == 4) RET(TSW_EINVAL, "k_bfs_big does not fit this grid (forced kernel big)");
-  Timer t(c, CAT_BFS);
-  if (nwv == 0) {
-    HIPCHK(launch_bfs(c->G, goals, slots, k, dist, dstride, nh, dstride, &c->d_stat->err, c->max_lds, c->num_cu,
-                      c->s, govf));
-    return TSW_OK;
-  }
-  TRY(ensure_wave_scratch(c, (uint64_t)c->num_cu * nwv, (size_t)c->npw * 32u, (size_t)c->npw * 2u));
+  TRY(grow_synced(c, c->d_mg_grp, c->h_mg_grp.size()));
+  HIPCHK(hipMemcpyAsync(c->d_mg_grp, c->h_mg_grp.data(), c->h_mg_grp.size() * 4u, hipMemcpyHostToDevice, c->s));
+  TRY(bfs_begin(c, J, true));
+  MgBfsArgs A{};
+  bfs_fill(A, J);
+  A.W = c->G.W;
+  A.H = c->G.H;
+  A.Bp = c->Bp;
+  A.nbp = c->nbp;
+  A.bp_magic = bp_magic(c->Bp);
+  A.frb = c->d_frb;
+  A.abase = c->d_abase;
+  A.nrs = std::max<uint32_t>(c->nrs, 1u);
+  A.grp = c->d_mg_grp;
+  A.ngroups = ngroups;
+  A.wl = c->d_mg_wl;
+  A.wlw = wlw;
+  A.anch = c->d_mg_anch;
+  A.scratch_wgs = c->mg_wgs;
+  A.prof = J.prof;
+  HIPCHK(launch_bfs_mg(A, c->max_lds, c->num_cu, c->s));
+  // the host copy of the group offsets must outlive the async upload
+  HIPCHK(hipStreamSynchronize(c->s));
+  return bfs_finish(c, J, "k_bfs_mg");
+}
+
+// one wave per goal over 8x8 blocks
+static int run_bfs_blk(tsw_ctx* c, BfsJob& J, const BfsChoice& ch) {
+  // scratch per goal slot: one per wave, two with TSW_BFS_PAIR
+  TRY(ensure_wave_scratch(c, (uint64_t)c->num_cu * ch.waves_per_block * (ch.pair ? 2u : 1u), std::max<size_t>(c->nrs, 1),
+                          (size_t)c->nbp * 2u));
+  TRY(ensure_wlg(c));
+  TRY(bfs_begin(c, J, true));
+  BlkBfsArgs A{};
+  bfs_fill_goals(A, J);
+  A.W = c->G.W;
+  A.H = c->G.H;
+  A.BW = c->BW;
+  A.BH = c->BH;
+  A.Bp = c->Bp;
+  A.nbp = c->nbp;
+  A.cap = ch.cap;
+  A.frb = c->d_frb;
+  A.abase = c->d_abase;
+  A.nrs = c->nrs;
+  A.anch = c->d_anch;
+  A.lovf = c->d_lovf;
+  A.wlg = c->d_wlg;
+  A.stage = (J.dstride % 8u == 0u && ((uintptr_t)J.dist & 15u) == 0u && !c->tun.bfs_nostage) ? 1u : 0u;
+  A.dbg = c->tun.bfs_dbg;
+  A.wls = c->tun.bfs_wls;
+  A.pair = ch.pair ? 1u : 0u;
+  A.max_waves = ch.waves_per_block;
+  A.scratch_waves = std::min(c->wave_scratch, c->wlg_waves);
+  A.prof = J.prof;
+  HIPCHK(launch_bfs_blk(A, c->max_lds, c->num_cu, c->s));
+  return bfs_finish(c, J, "k_bfs_blk");
+}
+
+// large grids (e.g. 1024x1024): one workgroup per goal, shared visited bitmap in LDS
+static int run_bfs_big(tsw_ctx* c, BfsJob& J, const BfsChoice& ch) {
+  const uint32_t nwg = bfs_big_workgroups(c->nbp, ch.cap, c->num_cu);
+  TRY(ensure_wave_scratch(c, nwg, std::max<size_t>(c->nrs, 1), (size_t)c->nbp * 2u));
+  TRY(ensure_wlg(c));
+  TRY(bfs_begin(c, J, false));
+  BigBfsArgs A{};
+  bfs_fill_goals(A, J);
+  A.W = c->G.W;
+  A.H = c->G.H;
+  A.BW = c->BW;
+  A.BH = c->BH;
+  A.Bp = c->Bp;
+  A.nbp = c->nbp;
+  A.cap = ch.cap;
+  A.frb = c->d_frb;
+  A.abase = c->d_abase;
+  A.nrs = std::max<uint32_t>(c->nrs, 1u);
+  A.anch = c->d_anch;
+  A.lovf = c->d_lovf;
+  A.wlg = reinterpret_cast<uint64_t*>(c->d_wlg.p);
+  A.scratch_wgs = (uint32_t)std::min<uint64_t>(c->wave_scratch, c->wlg_waves);
+  HIPCHK(launch_bfs_big(A, c->max_lds, c->num_cu, c->s));
+  return bfs_finish(c, J, "k_bfs_big");
+}
+
+// one wave per goal over row words
+static int run_bfs_wave(tsw_ctx* c, BfsJob& J, const BfsChoice& ch) {
+  TRY(ensure_wave_scratch(c, (uint64_t)c->num_cu * ch.waves_per_block, (size_t)c->npw * 32u, (size_t)c->npw * 2u));
+  TRY(bfs_begin(c, J, true));
   WaveBfsArgs A{};
+  bfs_fill_goals(A, J);
   A.W = c->G.W;
   A.H = c->G.H;
   A.Ww = c->G.Ww;
   A.Wp = c->Wp;
   A.npw = c->npw;
-  A.cap = c->tun.bfs_cap;
+  A.cap = ch.cap;
   A.frp = c->d_frp;
-  A.goals = goals;
-  A.slots = slots;
-  A.k = k;
-  A.dist = dist;
-  A.dstride = dstride;
   A.anch = c->d_anch;
   A.lovf = c->d_lovf;
-  A.work = &c->d_stat->work;
-  A.err = &c->d_stat->err;
-  A.govf = govf;
-  A.vec16 = vec16 ? 1u : 0u;
-  A.max_waves = max_waves;
+  A.max_waves = c->tun.bfs_waves;
   A.scratch_waves = c->wave_scratch;
-  A.prof = (uint64_t*)bfs_prof_buf(c);
-  HIPCHK(hipMemsetAsync(&c->d_stat->work, 0, 4, c->s));
+  A.prof = J.prof;
   HIPCHK(launch_bfs_wave(A, c->max_lds, c->num_cu, c->s));
-  if (A.prof) TRY(bfs_prof_print(c, "k_bfs_wave", k));
-  if (nh) HIPCHK(launch_classify(c->G, goals, slots, k, dist, dstride, nh, c->s));
+  return bfs_finish(c, J, "k_bfs_wave");
+}
+
+// What a forced kernel that does not fit the grid is refused with; nullptr for k_bfs, the last resort of the
+// auto mode, whose own launcher reports a misfit.
+static const char* bfs_misfit(BfsKernel k) {
+  switch (k) {
+    case BFS_MG: return "k_bfs_mg does not fit this grid (forced kernel mg)";
+    case BFS_BLK: return "k_bfs_blk does not fit this grid (forced kernel blk)";
+    case BFS_WAVE: return "k_bfs_wave does not fit this grid (forced kernel wave)";
+    case BFS_BIG: return "k_bfs_big does not fit this grid (forced kernel big)";
+    case BFS_BLOCK: break;
+  }
+  return nullptr;
+}
+
+// K1 over k goals (device arrays; slots may be null = goal index) with the kernel choose_bfs picks for this
+// grid (tsw_place.h). Next-hop codes (nh != null) come fused from k_bfs, or from k_classify over the
+// finished tables after the other kernels.
+static int run_bfs(tsw_ctx* c, const uint32_t* goals, const uint32_t* slots, uint32_t k, uint16_t* dist, uint64_t dstride,
+                   uint8_t* nh, uint8_t* govf = nullptr) {
+  if (k == 0) return TSW_OK;
+  BfsChoice ch = bfs_choice(c);
+  // k_bfs_mg runs the groups of bfs_mg_order: a launch whose order did not come from there has none
+  if (ch.kernel == BFS_MG && (c->h_mg_grp.empty() || c->h_mg_grp.back() != k)) ch.fits = false;
+  if (!ch.fits && bfs_misfit(ch.kernel)) RET(TSW_EINVAL, bfs_misfit(ch.kernel));
+  const bool vec16 = c->G.W % 8u == 0u && dstride % 8u == 0u && ((uintptr_t)dist & 15u) == 0u;
+  BfsJob J{goals, slots, k, dist, dstride, nh, govf, vec16 ? 1u : 0u, &c->d_stat->work, &c->d_stat->err, nullptr};
+  Timer t(c, CAT_BFS);
+  switch (ch.kernel) {
+    case BFS_MG: return run_bfs_mg(c, J);
+    case BFS_BLK: return run_bfs_blk(c, J, ch);
+    case BFS_WAVE: return run_bfs_wave(c, J, ch);
+    case BFS_BIG: return run_bfs_big(c, J, ch);
+    case BFS_BLOCK:
+      HIPCHK(launch_bfs(c->G, goals, slots, k, dist, dstride, nh, dstride, &c->d_stat->err, c->max_lds, c->num_cu, c->s, govf));
+  }
   return TSW_OK;
 }
 

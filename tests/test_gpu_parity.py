@@ -217,7 +217,9 @@ def test_mapd_global_agent_arrays():
 @pytest.mark.parametrize("split", ["1", "0"])
 def test_mapd_occ_placement(split, monkeypatch):
     """170x84 warehouse: the occupancy grid in LDS without the movement rounds' MU words (default,
-    k_plan<.., OC, !MUL>) and both in global memory (TSW_OCC_SPLIT=0), 400 agents, bit-exact."""
+    k_plan<.., OC, !MUL>) and both in global memory (TSW_OCC_SPLIT=0), 400 agents, bit-exact. On a device with 160 KiB
+    of LDS the agent arrays, OCC and MU all fit (131,184 B) whatever the knob says, so both cases run k_plan<AG, OC, MUL>:
+    tests/test_place.py pins that placement."""
     monkeypatch.setenv("TSW_OCC_SPLIT", split)
     rows = maps.warehouse_map(170, 84, 0x170084)
     starts, tasks = maps.make_instance(rows, 400, 1200, 0x400)
@@ -411,8 +413,8 @@ def test_mapd_partial_lds_agent_arrays(monkeypatch, mask):
 @pytest.mark.parametrize("n,side,part", [(1000, 150, None), (1000, 200, None), (6000, 100, "0")],
                          ids=["ag_occ", "ag", "occ_mu"])
 def test_mapd_lds_placements(monkeypatch, n, side, part):
-    """The k_plan instantiations that the cases above do not reach, by what fits LDS (choose_plan_lds; run with
-    TSW_PLAN_DEBUG the diagnostic library prints the placement): 1,000 agents on a 150x150 grid — the agent arrays
+    """The k_plan instantiations that the cases above do not reach, by what fits LDS (choose_plan_placement,
+    csrc/tsw_place.h; tests/test_place.py pins the placement and the instantiation of each case on the CPU): 1,000 agents on a 150x150 grid — the agent arrays
     and the occupancy grid but not the movement rounds' MU words beside them, k_plan<AG, OC, !MUL>; on a 200x200
     grid — the agent arrays alone, k_plan<AG, !OC>; 6,000 agents on a 100x100 grid with no agent array admitted
     (TSW_PART_LDS=0) — the agent arrays in global memory, OCC and MU (8 B a cell) in LDS, k_plan<!AG, OC, MUL, !PG>
