@@ -67,7 +67,8 @@ extern "C" {
  * 7: tsw_opts.reserved became host_astar, tsw_stats gained host_astar_queries / host_astar_used /
  * host_astar_ms, tsw_host_next_hop_codes; 8: tsw_nearby, tsw_decide_fleet. Still 8: tsw_fleet_apply and
  * tsw_fleet_run, and after them tsw_fleet_mapd, were added without touching a struct or an existing
- * signature, and so were tsw_audit_records and tsw_audit_records_device (one new struct, tsw_audit); a
+ * signature, and so were tsw_audit_records and tsw_audit_records_device (one new struct, tsw_audit), and
+ * then tsw_plan_mapd_online (no struct, no existing signature touched); a
  * caller that wants them looks the symbols up (dlsym) instead of comparing the revision. */
 #define TSW_ABI_VERSION 8
 
@@ -164,6 +165,27 @@ int tsw_plan_mapd(tsw_ctx *ctx, const tsw_point *starts, uint32_t n, const tsw_t
 int tsw_plan_mapd_trace(tsw_ctx *ctx, const tsw_point *starts, uint32_t n, const tsw_task *tasks,
                         uint32_t m, uint32_t max_t, tsw_rec *out, uint32_t *goal_out,
                         uint32_t *out_T);
+
+/* Online MAPD: tswap_mapd (tswap.rs:39-172) with a release time per task. release[k] is the first
+ * iteration that sees task k; release == NULL means every task is released at 0. Two changes to the loop:
+ *   1. Visibility. Iteration t is the one that produces column t. Its nearest-pickup scan (:123-131)
+ *      skips every task k with release[k] > t. Among the visible unused tasks the choice is unchanged:
+ *      minimum Manhattan distance to the raw pickup point, lowest task index on ties. Release times do
+ *      not reorder tasks.
+ *   2. Termination (:163-169). The run ends after recording column t when every task is used (a task
+ *      not yet released is not used) and every agent is idle, or when t + 1 > max_t. A fleet that is idle
+ *      while tasks are still to come keeps producing columns: tswap_step still runs, so an idle agent that
+ *      a goal swap sent elsewhere walks on; once every agent rests on its goal the columns repeat
+ *      (state TSW_IDLE).
+ * So: release all zero (or NULL) gives exactly tsw_plan_mapd_trace's output; a task with release > max_t
+ * is never seen, and the run then ends at max_t with *out_T = max_t + 1; task cells are looked up lazily
+ * as in tsw_plan_mapd (a bad pickup fails the call with TSW_EINVAL when it is assigned, a bad delivery
+ * when its agent reaches the pickup, a bad task that is never released never). Everything else is
+ * tsw_plan_mapd_trace's: the record layout, goal_out (may be NULL), max_t <= 2^20, the argument checks,
+ * the refusal of re-entry from a resolver. */
+int tsw_plan_mapd_online(tsw_ctx *ctx, const tsw_point *starts, uint32_t n, const tsw_task *tasks,
+                         const uint32_t *release, uint32_t m, uint32_t max_t, tsw_rec *out,
+                         uint32_t *goal_out, uint32_t *out_T);
 
 /* Caller-resolved K3 (the per-step query batch sharded by goal owner, the
  * answers gathered). tsw_plan_mapd_resolved plans like tsw_plan_mapd_trace, in exit mode (no K3

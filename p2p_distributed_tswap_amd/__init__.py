@@ -144,7 +144,7 @@ EXPORTED_SYMBOLS = (
     "tsw_clear_tables", "tsw_get_stats", "tsw_reset_stats", "tsw_set_timing", "tsw_probe_round_floors",
     "tsw_abi_version", "tsw_plan_mapd_resolved", "tsw_next_hop_codes", "tsw_build_id",
     "tsw_host_next_hop_codes", "tsw_nearby", "tsw_decide_fleet", "tsw_fleet_apply", "tsw_fleet_run",
-    "tsw_fleet_mapd", "tsw_audit_records", "tsw_audit_records_device",
+    "tsw_fleet_mapd", "tsw_audit_records", "tsw_audit_records_device", "tsw_plan_mapd_online",
 )
 
 # tsw_resolve_fn (include/tswap.h): int (*)(void *user, uint32_t k, const uint32_t *start,
@@ -183,6 +183,8 @@ def load_library(path: str = LIB_PATH):
     lib.tsw_last_error.restype = ctypes.c_char_p
     lib.tsw_plan_mapd.argtypes = [vp, P(_Point), u32, P(_Task), u32, u32, P(_Rec), P(u32)]
     lib.tsw_plan_mapd_trace.argtypes = [vp, P(_Point), u32, P(_Task), u32, u32, P(_Rec), P(u32), P(u32)]
+    lib.tsw_plan_mapd_online.argtypes = [vp, P(_Point), u32, P(_Task), P(u32), u32, u32, P(_Rec), P(u32), P(u32)]
+    lib.tsw_plan_mapd_online.restype = ctypes.c_int
     lib.tsw_step.argtypes = [vp, P(u32), P(u32), u32]
     lib.tsw_get_path_next.argtypes = [vp, P(u32), P(u32), u32, P(u32), P(i32)]
     lib.tsw_decide.argtypes = [vp, P(u32), P(u32), u32, P(u32), P(u32), P(u32), P(u32), P(u32), P(u32), P(u32),
@@ -335,6 +337,32 @@ class Planner:
         else:
             rc = self._lib.tsw_plan_mapd(self._ctx, sp, n, tp, m, max_t, op, ctypes.byref(T))
         self._check(rc)
+        t = T.value
+        rec = out[:n, :t] & np.uint64(0xFFFFFFFFFF)
+        return rec, (goals[:n, :t] if goals is not None else None)
+
+    def plan_mapd_online(self, starts_xy: np.ndarray, tasks_xyxy: np.ndarray, release, max_t: int = 2000,
+                         trace_goals: bool = False):
+        """tsw_plan_mapd_online: as plan_mapd_arrays, with task k visible from iteration release[k] on
+        (release: (m,) uint32; None: every task at 0). The run goes on while tasks are still to come, so
+        it ends when every task is used and every agent idle, or at max_t. Returns what plan_mapd_arrays
+        returns."""
+        starts = np.ascontiguousarray(starts_xy, dtype=np.uint32).reshape(-1, 2)
+        tasks = np.ascontiguousarray(tasks_xyxy, dtype=np.uint32).reshape(-1, 4)
+        n, m = starts.shape[0], tasks.shape[0]
+        rel = None
+        if release is not None:
+            rel = np.ascontiguousarray(release, dtype=np.uint32).reshape(-1)
+            if rel.size != m:
+                raise TswapError(TSW_EINVAL, "release must hold one time per task")
+        stride = max_t + 1
+        out = np.zeros((max(n, 1), stride), dtype=np.uint64)
+        goals = np.zeros((max(n, 1), stride), dtype=np.uint32) if trace_goals else None
+        T = ctypes.c_uint32(0)
+        self._check(self._lib.tsw_plan_mapd_online(
+            self._ctx, starts.ctypes.data_as(ctypes.POINTER(_Point)), n, tasks.ctypes.data_as(ctypes.POINTER(_Task)),
+            _u32p(rel) if rel is not None else None, m, max_t, out.ctypes.data_as(ctypes.POINTER(_Rec)),
+            _u32p(goals) if goals is not None else None, ctypes.byref(T)))
         t = T.value
         rec = out[:n, :t] & np.uint64(0xFFFFFFFFFF)
         return rec, (goals[:n, :t] if goals is not None else None)

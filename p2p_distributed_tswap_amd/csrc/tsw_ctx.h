@@ -1,7 +1,8 @@
-// tsw_ctx.h — the host runtime's context (struct tsw_ctx behind include/tswap.h) and what its six
+// tsw_ctx.h — the host runtime's context (struct tsw_ctx behind include/tswap.h) and what its seven
 // translation units share: tsw_ctx.hip (create / destroy, tunables, stats), tsw_tables.hip (K1 and the
 // goal-table store), tsw_query.hip (K3 scratch, queue and passes), tsw_plan_host.hip (the plan runner and
-// its host A* service), tsw_fleet_host.hip (decide and the fleet entry points) and tsw_audit_host.hip (the
+// its host A* service), tsw_online_host.hip (the plan with release times, run in segments),
+// tsw_fleet_host.hip (decide and the fleet entry points) and tsw_audit_host.hip (the
 // audit of plan records). Host code only; every
 // device buffer of the context is a DevBuf / PinnedBuf member (tsw_buf.h) and is freed with it.
 // Nothing here depends on the build flavour: only tsw_ctx.hip is compiled per flavour.
@@ -253,6 +254,8 @@ struct tsw_ctx {
   DevBuf<uint32_t> d_klt, d_kpos, d_kcnt;
   DevBuf<uint2> d_kbox;
   uint32_t kchunks = 0;
+  // tsw_plan_mapd_online: the tasks in release order and their clamped pickup points, uploaded once per call
+  DevBuf<uint32_t> d_rel_order, d_pxy;
   // records
   DevBuf<uint64_t> d_rec;
   DevBuf<uint32_t> d_grec;
@@ -337,6 +340,50 @@ int reset_pending_after(tsw_ctx* c, int rc);
 int resolve_all_unknown(tsw_ctx* c, const std::vector<uint32_t>& goals, const std::vector<uint32_t>& slots);
 bool eager_policy(const tsw_ctx* c, size_t new_tables);
 int resolve_queue(tsw_ctx* c, const AstarQuery* Q, uint32_t nq);
+
+// tsw_plan_host.hip: a MAPD plan call in parts (plan_impl runs them once; tsw_online_host.hip runs the
+// dispatch part once per segment)
+// What one k_plan launch needs beside PlanArgs. Rebuilt when a call falls back from coop to exit mode.
+struct Dispatch {
+  size_t lds = 0;      // the planner block's dynamic LDS
+  uint32_t block = 0;  // its threads
+  WorkerArgs W{};      // coop mode: the K3 workers of workgroups 1..wblocks
+  uint32_t wblocks = 0;
+  bool serve = false;  // host A* service on
+};
+
+// K4 spatial index: the tasks in Morton order of their (clamped) pickup points pxy (x | y << 16), cut into
+// chunks of 32 entries (k_plan's KCH) with static bounding boxes and counts (tsw_plan.h PlanArgs::kbox).
+// Padding entries of the last chunk stay TASK_TAKEN; no task still gives one (empty) chunk.
+struct TaskIndex {
+  std::vector<uint32_t> live, klt, kpos, kcnt;
+  std::vector<uint2> kbox;
+};
+
+struct PlanCall {
+  std::chrono::steady_clock::time_point t0;  // the call's start (tsw_stats plan_ms)
+  uint32_t n = 0, m = 0, max_t = 0;
+  bool want_goals = false;
+  std::vector<uint32_t> vcell, pick, dlv, pxy;  // start cells; task cells (CELL_BAD: looked up lazily); pickup points
+  std::vector<uint32_t> goalset;                // every cell that can become a goal
+  TaskIndex ix;
+  PlanArgs P{};
+  Dispatch D;
+  bool dispatched = false;  // D is set up (the first segment does it)
+};
+// the argument checks, the cells of starts and tasks, the K4 index over all m tasks
+int plan_validate_index(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_task* tasks, uint32_t m, uint32_t max_t,
+                        tsw_rec* out, uint32_t* goal_out, uint32_t* out_T, PlanCall* call);
+// agent and task state and the index on the device; the record buffers sized for max_t + 1 columns
+int plan_upload(tsw_ctx* c, PlanCall& call);
+// occupancy, goal tables, queues, coop buffers and task chains; PlanArgs. chain_order (m task indices) /
+// chain_at (out: m + 1 entries, chains among the first j tasks of the order): the chains in that order
+int plan_tables(tsw_ctx* c, PlanCall& call, const uint32_t* chain_order = nullptr, std::vector<uint32_t>* chain_at = nullptr);
+// k_plan from `init` until it reports done (one segment); failures reset pending codes
+int plan_segment(tsw_ctx* c, PlanCall& call, const PlanCtl& init);
+// t columns into the caller's arrays, *out_T, the call's stats
+int plan_download(tsw_ctx* c, PlanCall& call, uint32_t t, tsw_rec* out, uint32_t* goal_out, uint32_t* out_T);
+void plan_phase(tsw_ctx* c, const PlanCall& call, const char* what);  // TSW_PLAN_DEBUG: host-side phases
 
 // A grow-only buffer of the context that kernels of earlier calls may still use: the stream is drained
 // before the old block goes (DevBuf::grow itself never synchronises).

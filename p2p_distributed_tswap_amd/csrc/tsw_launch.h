@@ -1,5 +1,5 @@
 // tsw_launch.h — host-callable launch wrappers of the K1 (tsw_bfs*.hip), classification (tsw_classify.hip), K3
-// (tsw_astar.hip), code-store (tsw_codes.hip), decision (tsw_decide.hip) and probe kernels, with the K1 argument
+// (tsw_astar.hip), code-store (tsw_codes.hip), decision (tsw_decide.hip), online-release (tsw_online.hip) and probe kernels, with the K1 argument
 // structs. What fits where, and which kernel a launch takes, is tsw_place.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -186,6 +186,13 @@ hipError_t launch_decide(const DecideArgs& A, hipStream_t s);
 hipError_t launch_enqueue_unknown(const DevGrid& G, const uint32_t* goals, const uint32_t* slots, uint32_t k,
                                   uint8_t* nh, uint64_t nstride, AstarQuery* Q, uint32_t* qcount,
                                   uint32_t qcap, hipStream_t s);
+
+// Between the k_plan segments of tsw_plan_mapd_online (tsw_online.hip): tasks rel_order[lo .. hi) become live
+// entries of the K4 index (live[kpos[k]] = pxy[k], their chunk's kcnt + 1); columns t_from .. t_to - 1 of the
+// timestep-major records (and of grec, may be null) repeat column t_from - 1.
+hipError_t launch_task_release(const uint32_t* rel_order, uint32_t lo, uint32_t hi, const uint32_t* kpos,
+                               const uint32_t* pxy, uint32_t* live, uint32_t* kcnt, hipStream_t s);
+hipError_t launch_rec_hold(uint64_t* rec, uint32_t* grec, uint32_t n, uint32_t t_from, uint32_t t_to, hipStream_t s);
 
 // Latency floors of k_plan's round shapes (tsw_probe.hip): us per wave-0 rules firing chain and per
 // block-wide pass (LDS exchange + barrier) on a `block`-thread workgroup.

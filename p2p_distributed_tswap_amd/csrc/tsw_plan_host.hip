@@ -239,15 +239,7 @@ static void host_service_end(tsw_ctx* c) {
 }
 
 // ---- the plan dispatch -------------------------------------------------------------------------
-// What one k_plan launch needs beside PlanArgs. Rebuilt when a call falls back from coop to exit mode.
-struct Dispatch {
-  size_t lds = 0;      // the planner block's dynamic LDS
-  uint32_t block = 0;  // its threads
-  WorkerArgs W{};      // coop mode: the K3 workers of workgroups 1..wblocks
-  uint32_t wblocks = 0;
-  bool serve = false;  // host A* service on
-};
-
+// (Dispatch, what one k_plan launch needs beside PlanArgs: tsw_ctx.h.)
 // Coop mode: the K3 workers' arguments and their count for a planner block of `block` threads and `lds` bytes.
 // Sets P.spec_hi; clears P.coop (exit mode) when nothing fits beside the planner.
 static int worker_args(tsw_ctx* c, PlanArgs& P, size_t lds, uint32_t block, WorkerArgs* Wp, uint32_t* wblocks) {
@@ -583,11 +575,10 @@ static int plan_error(tsw_ctx* c, const PlanCtl& k) {
 // a planner that gave up waiting has its needed queue resolved here and is relaunched. Exit mode: each
 // NEED_QUERIES exit runs K3 on the queued pairs. After a watchdog firing a coop call goes on in exit mode.
 // Every return happens after the dispatch has drained (workers included): nothing of this call keeps
-// running into the next one.
-static int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
-  Dispatch D;
+// running into the next one. setup: D is built here (a later segment of the same call reuses it).
+static int run_plan_impl(tsw_ctx* c, PlanArgs& P, Dispatch& D, bool setup, const PlanCtl& init) {
   TRY(upload_ctl(c, init));
-  TRY(setup_dispatch(c, P, &D));
+  if (setup) TRY(setup_dispatch(c, P, &D));
   uint64_t bound = 16ull * P.n + 4096ull * (init.max_t + 1);  // launches without reaching the end
   for (uint64_t launches = 0;;) {
     if (launches > bound) RET(TSW_EINVAL, "plan kernel made no progress");
@@ -658,17 +649,11 @@ static int run_plan_impl(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
 
 // Any failure after k_plan queued pairs leaves their codes PENDING: reset them.
 static int run_plan(tsw_ctx* c, PlanArgs& P, const PlanCtl& init) {
-  return reset_pending_after(c, run_plan_impl(c, P, init));
+  Dispatch D;
+  return reset_pending_after(c, run_plan_impl(c, P, D, true, init));
 }
 
-// K4 spatial index: the tasks in Morton order of their (clamped) pickup points pxy (x | y << 16), cut into
-// chunks of 32 entries (k_plan's KCH) with static bounding boxes and counts (tsw_plan.h PlanArgs::kbox).
-// Padding entries of the last chunk stay TASK_TAKEN; no task still gives one (empty) chunk.
-struct TaskIndex {
-  std::vector<uint32_t> live, klt, kpos, kcnt;
-  std::vector<uint2> kbox;
-};
-
+// The K4 spatial index (TaskIndex, tsw_ctx.h) of the tasks' pickup points.
 static TaskIndex build_task_index(const std::vector<uint32_t>& pxy) {
   constexpr uint32_t KCHH = 32;
   const uint32_t m = (uint32_t)pxy.size(), nch = std::max<uint32_t>((m + KCHH - 1u) / KCHH, 1u);
@@ -764,13 +749,18 @@ static int upload_plan_inputs(tsw_ctx* c, uint32_t n, uint32_t m, const std::vec
 
 // Coop mode: every task's pickup -> delivery path, resolved hop by hop by the workers in the background
 // (lowest priority): an agent that picks the task up finds its next hops already there. Also grows the hot
-// and the predicted chains' queues.
+// and the predicted chains' queues. The chains are queued in task index order, or in `order` (m task
+// indices); chain_at, when given, gets m + 1 entries: the chains among the first j tasks of that order.
 static int queue_task_chains(tsw_ctx* c, uint32_t n, uint32_t m, const std::vector<uint32_t>& pick,
-                             const std::vector<uint32_t>& dlv) {
+                             const std::vector<uint32_t>& dlv, const uint32_t* order, std::vector<uint32_t>* chain_at) {
   std::vector<AstarQuery> qt;
   qt.reserve(m);
-  for (uint32_t k = 0; k < m; ++k)
+  if (chain_at) chain_at->assign((size_t)m + 1u, 0u);
+  for (uint32_t j = 0; j < m; ++j) {
+    const uint32_t k = order ? order[j] : j;
     if (pick[k] != dlv[k] && pick[k] != CELL_BAD && dlv[k] != CELL_BAD) qt.push_back(AstarQuery{pick[k], dlv[k], c->h_goal_tab[dlv[k]], 0u});
+    if (chain_at) (*chain_at)[j + 1u] = (uint32_t)qt.size();
+  }
   if (qt.size() > c->d_QT.cap) {
     HIPCHK(hipStreamSynchronize(c->s));
     HIPCHK(c->d_QT.grow(qt.size()));
@@ -788,15 +778,24 @@ static int queue_task_chains(tsw_ctx* c, uint32_t n, uint32_t m, const std::vect
   return TSW_OK;
 }
 
-// validate -> index -> upload -> tables -> dispatch -> records
-static int plan_impl(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_task* tasks, uint32_t m,
-              uint32_t max_t, tsw_rec* out, uint32_t* goal_out, uint32_t* out_T) {
-  auto t0 = std::chrono::steady_clock::now();
+// ---- a MAPD plan call in parts (tsw_ctx.h): validate and index -> upload -> tables -> dispatch -> records ----
+void plan_phase(tsw_ctx* c, const PlanCall& call, const char* what) {
+  if (c->tun.plan_debug)
+    fprintf(stderr, "[plan] %s at %.1f ms\n", what,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call.t0).count());
+}
+
+int plan_validate_index(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_task* tasks, uint32_t m, uint32_t max_t,
+                        tsw_rec* out, uint32_t* goal_out, uint32_t* out_T, PlanCall* call) {
+  call->t0 = std::chrono::steady_clock::now();
   if (!out_T || (n && (!starts || !out)) || (m && !tasks)) RET(TSW_EINVAL, "null argument");
   if (max_t > (1u << 20)) RET(TSW_EINVAL, "max_t too large");
   TRY(set_device(c));
-  std::vector<uint32_t> vcell(n), pick(m), dlv(m), pxy(m);
-  std::vector<uint32_t> goalset;
+  call->n = n, call->m = m, call->max_t = max_t;
+  call->want_goals = goal_out != nullptr;
+  std::vector<uint32_t>&vcell = call->vcell, &pick = call->pick, &dlv = call->dlv, &pxy = call->pxy, &goalset = call->goalset;
+  vcell.assign(n, 0u), pick.assign(m, 0u), dlv.assign(m, 0u), pxy.assign(m, 0u);
+  goalset.clear();
   goalset.reserve(n + 2 * (size_t)m);
   for (uint32_t i = 0; i < n; ++i) {
     if (!cell_ok(c, starts[i].x, starts[i].y, &vcell[i]))
@@ -817,45 +816,68 @@ static int plan_impl(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_
     if (pick[k] != CELL_BAD) goalset.push_back(pick[k]);
     if (dlv[k] != CELL_BAD) goalset.push_back(dlv[k]);
   }
-  const TaskIndex ix = build_task_index(pxy);
-  TRY(upload_plan_inputs(c, n, m, vcell, pick, dlv, ix));
-  const size_t stride_t = (size_t)max_t + 1;
-  const size_t recs = stride_t * std::max<uint32_t>(n, 1);
+  call->ix = build_task_index(pxy);
+  return TSW_OK;
+}
+
+int plan_upload(tsw_ctx* c, PlanCall& call) {
+  TRY(upload_plan_inputs(c, call.n, call.m, call.vcell, call.pick, call.dlv, call.ix));
+  const size_t recs = ((size_t)call.max_t + 1) * std::max<uint32_t>(call.n, 1);
   TRY(grow_synced(c, c->d_rec, recs));
-  if (goal_out) TRY(grow_synced(c, c->d_grec, recs));
-  auto tphase = [&](const char* what) {  // diagnostics (TSW_PLAN_DEBUG): host-side phases of the call
-    if (c->tun.plan_debug)
-      fprintf(stderr, "[plan] %s at %.1f ms\n", what,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  };
-  tphase("inputs uploaded");
+  if (call.want_goals) TRY(grow_synced(c, c->d_grec, recs));
+  plan_phase(c, call, "inputs uploaded");
+  return TSW_OK;
+}
+
+int plan_tables(tsw_ctx* c, PlanCall& call, const uint32_t* chain_order, std::vector<uint32_t>* chain_at) {
+  const uint32_t n = call.n, m = call.m;
   TRY(build_occ(c, n));
-  TRY(ensure_tables(c, goalset, true));
+  TRY(ensure_tables(c, call.goalset, true));
   HIPCHK(hipStreamSynchronize(c->s));
-  tphase("tables built");
+  plan_phase(c, call, "tables built");
   TRY(ensure_queue(c, 4 * (size_t)n + 4096));  // needed pairs (<= 2n per exit) + speculative prefetch (qcap/2)
   c->qt_count = 0;
+  if (chain_at) chain_at->clear();
   if (c->tun.coop && !c->resolver && !eager_policy(c, 0)) {
-    TRY(ensure_coop(c, n, max_t));
-    if (c->tun.task_chains && m) TRY(queue_task_chains(c, n, m, pick, dlv));
+    TRY(ensure_coop(c, n, call.max_t));
+    if (c->tun.task_chains && m) TRY(queue_task_chains(c, n, m, call.pick, call.dlv, chain_order, chain_at));
   }
-  PlanArgs P = plan_args(c, n, m, MODE_MAPD, goal_out != nullptr);
+  call.P = plan_args(c, n, m, MODE_MAPD, call.want_goals);
+  call.dispatched = false;
+  return TSW_OK;
+}
+
+int plan_segment(tsw_ctx* c, PlanCall& call, const PlanCtl& init) {
+  const bool setup = !call.dispatched;
+  call.dispatched = true;
+  return reset_pending_after(c, run_plan_impl(c, call.P, call.D, setup, init));
+}
+
+int plan_download(tsw_ctx* c, PlanCall& call, uint32_t t, tsw_rec* out, uint32_t* goal_out, uint32_t* out_T) {
+  c->st.steps += t;
+  *out_T = t;
+  if (call.n) TRY(download_records(c, call.n, t, (size_t)call.max_t + 1, out, goal_out));
+  resolve_timing(c);
+  c->st.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call.t0).count();
+  return TSW_OK;
+}
+
+static int plan_impl(tsw_ctx* c, const tsw_point* starts, uint32_t n, const tsw_task* tasks, uint32_t m,
+              uint32_t max_t, tsw_rec* out, uint32_t* goal_out, uint32_t* out_T) {
+  PlanCall call;
+  TRY(plan_validate_index(c, starts, n, tasks, m, max_t, out, goal_out, out_T, &call));
+  TRY(plan_upload(c, call));
+  TRY(plan_tables(c, call));
   PlanCtl init{};
   init.section = SEC_ASSIGN;
   init.unused = m;
   init.max_t = max_t;
   init.chase_id = c->chase_id;
   init.move_rounds = c->tun.move_round0;
-  tphase("plan dispatch starts");
-  TRY(run_plan(c, P, init));
-  tphase("plan dispatch done");
-  const uint32_t t = c->h_ctl->t;
-  c->st.steps += t;
-  *out_T = t;
-  if (n) TRY(download_records(c, n, t, stride_t, out, goal_out));
-  resolve_timing(c);
-  c->st.plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return TSW_OK;
+  plan_phase(c, call, "plan dispatch starts");
+  TRY(plan_segment(c, call, init));
+  plan_phase(c, call, "plan dispatch done");
+  return plan_download(c, call, c->h_ctl->t, out, goal_out, out_T);
 }
 
 }  // namespace tsw

@@ -176,6 +176,10 @@ extern "C" {
                          max_t: u32, out: *mut TswRec, out_t: *mut u32) -> c_int;
     pub fn tsw_plan_mapd_trace(ctx: *mut TswCtx, starts: *const TswPoint, n: u32, tasks: *const TswTask, m: u32,
                                max_t: u32, out: *mut TswRec, goal_out: *mut u32, out_t: *mut u32) -> c_int;
+    /// Online MAPD: task k is visible from iteration release[k] on (null: every task at 0).
+    pub fn tsw_plan_mapd_online(ctx: *mut TswCtx, starts: *const TswPoint, n: u32, tasks: *const TswTask,
+                                release: *const u32, m: u32, max_t: u32, out: *mut TswRec, goal_out: *mut u32,
+                                out_t: *mut u32) -> c_int;
     pub fn tsw_step(ctx: *mut TswCtx, v: *mut u32, g: *mut u32, n: u32) -> c_int;
     pub fn tsw_get_path_next(ctx: *mut TswCtx, start: *const u32, goal: *const u32, k: u32, next: *mut u32,
                              len: *mut i32) -> c_int;
