@@ -68,7 +68,8 @@ extern "C" {
  * host_astar_ms, tsw_host_next_hop_codes; 8: tsw_nearby, tsw_decide_fleet. Still 8: tsw_fleet_apply and
  * tsw_fleet_run, and after them tsw_fleet_mapd, were added without touching a struct or an existing
  * signature, and so were tsw_audit_records and tsw_audit_records_device (one new struct, tsw_audit), and
- * then tsw_plan_mapd_online (no struct, no existing signature touched); a
+ * then tsw_plan_mapd_online (no struct, no existing signature touched), and then tsw_task_timeline,
+ * tsw_task_timeline_device and tsw_probe_timeline (one new struct, tsw_timeline); a
  * caller that wants them looks the symbols up (dlsym) instead of comparing the revision. */
 #define TSW_ABI_VERSION 8
 
@@ -415,6 +416,75 @@ int tsw_audit_records(tsw_ctx *ctx, const tsw_rec *rec, uint32_t n, uint32_t T, 
                       tsw_audit *sum, uint32_t *col, uint32_t *agent);
 int tsw_audit_records_device(tsw_ctx *ctx, const tsw_rec *dev_rec, uint32_t n, uint32_t T,
                              uint32_t stride, tsw_audit *sum, uint32_t *col, uint32_t *agent);
+
+/* K8: the task timeline of plan records, on the device: which agent took each task, when it was assigned,
+ * picked up and delivered — the figures of the reference's src/map/task_metrics.rs (TaskMetric: sent_time is
+ * release, start_time is t_assign, completion_time is t_deliver, counted in steps). No plan entry point has to
+ * report them: the records determine them. rec, n, T, stride: as tsw_audit_records (only columns 0 .. T-1 are
+ * read, the pad bytes are ignored); any prefix of a run's columns is a valid input. starts, tasks, release, m:
+ * what the plan call was given (release == NULL: every task is released at 0).
+ * Internal states. S of a record is I for TSW_IDLE, P for TSW_PICKING, D for TSW_CARRYING or TSW_DELIVERED: the
+ * Idle / ToPickup / ToDelivery of tswap_mapd (tswap.rs:106-121). S(i, -1) = I. The position of agent i before
+ * iteration t is its (x, y) in column t-1, and starts[i] for t = 0 (a start coordinate above 0xFFFF is read
+ * as 0xFFFF, the most a record holds).
+ * Replay. Columns t = 0 .. T-1 in order, within a column the agents in ascending index; for agent i the
+ * transition p = S(i, t-1) -> c = S(i, t):
+ *   P->P, D->D        nothing
+ *   P->D              the agent's task is carried from t: t_carry = t
+ *   D->I, D->P        the agent's task is finished and the agent holds none; then dispatch
+ *   I->I, I->P        dispatch
+ *   P->I, I->D, or a record state > 3     inconsistency of kind 0
+ * Dispatch for agent i at column t, rule TSW_TL_NEAREST: the candidates are the tasks k that are not taken and
+ * have release[k] <= t. c = P with no candidate is an inconsistency of kind 1, c = I with a candidate one of
+ * kind 2. c = P with candidates takes the k with the smallest |x - px| + |y - py| from the agent's position,
+ * the lowest k on ties, where (px, py) is the raw pickup point with its coordinates clamped to 0xFFFE exactly
+ * as tsw_plan_mapd clamps them. A take sets agent[k] = i and t_assign[k] = t. Rule TSW_TL_STREAM: the one
+ * candidate is task `next` (0 at the start) while next < m, and a take is k = next++; kinds 1 and 2 alike;
+ * release must be NULL, starts is not read and may be NULL.
+ * Delivery. While agent i holds task k, the first column whose record is TSW_DELIVERED is t_deliver[k] (the
+ * agent is freed in iteration t_deliver + 1).
+ * "The agent's task" is the bookkeeping of agent_tasks[i] (tswap.rs:90, :134), as in the reference: TSWAP swaps
+ * goals, so the cell an agent stands on at t_carry - 1 may be another task's pickup, and the delivery cell
+ * another task's.
+ * task (may be NULL: only the summary): m * TSW_TL_NTASK words, task[k*4 + 0 .. 3] = agent, t_assign, t_carry,
+ * t_deliver; an event that did not happen is 0xFFFFFFFF. The replay stops at the first inconsistency in
+ * (t, agent) order: then consistent = 0, bad_kind / bad_t / bad_agent name it, task[] and the sums hold exactly
+ * the events strictly before that (t, agent), and the call still returns TSW_OK. Otherwise consistent = 1 and
+ * the three bad fields are 0xFFFFFFFF. Records that contradict the dispatch rule are found this way: the
+ * replay is an audit of the assignment.
+ * sum: assigned, carried, delivered count the tasks that have the corresponding time; unreleased the tasks with
+ * release > T - 1 (every task when T == 0); wait_sum is the sum of t_assign - release over the assigned tasks;
+ * service_sum, service_min, service_max are over t_deliver - release of the delivered tasks (none delivered:
+ * min 0xFFFFFFFF, max 0); carry_sum is the sum of t_deliver - t_carry; makespan the largest t_deliver
+ * (0xFFFFFFFF if none).
+ * TSW_EINVAL before anything is launched, the outputs untouched: a NULL sum; a NULL rec with n > 0 && T > 0; a
+ * NULL tasks with m > 0; a NULL starts with rule TSW_TL_NEAREST and n > 0 && T > 0; stride < T; T > 2^20 + 1;
+ * rule > 1; release != NULL with TSW_TL_STREAM; a context inside its own resolver. n == 0 or T == 0: TSW_OK
+ * with consistent = 1, nothing assigned, every task[] word 0xFFFFFFFF and unreleased as defined. TSW_ENOMEM
+ * when the scratch does not fit (one byte per record and 36 bytes per task). Like the audit the call reads no
+ * table and touches neither the table store, the queues nor the stats: a plan after a timeline equals a plan
+ * without one.
+ * tsw_task_timeline_device: the same with the records in DEVICE memory, read in place with their stride;
+ * every other argument is host memory in both forms. */
+#define TSW_TL_NEAREST 0u  /* tswap_mapd's dispatch (tswap.rs:123-137), with tsw_plan_mapd_online's visibility */
+#define TSW_TL_STREAM 1u  /* tsw_fleet_mapd's dispatch: the next task of the stream */
+#define TSW_TL_NTASK 4u  /* words per task in task[] */
+typedef struct {
+    uint64_t wait_sum, service_sum, carry_sum;
+    uint32_t assigned, carried, delivered, unreleased;
+    uint32_t service_min, service_max, makespan;
+    uint32_t consistent, bad_kind, bad_t, bad_agent;
+} tsw_timeline;
+int tsw_task_timeline(tsw_ctx *ctx, const tsw_rec *rec, uint32_t n, uint32_t T, uint32_t stride,
+                      const tsw_point *starts, const tsw_task *tasks, const uint32_t *release, uint32_t m,
+                      uint32_t rule, tsw_timeline *sum, uint32_t *task);
+int tsw_task_timeline_device(tsw_ctx *ctx, const tsw_rec *dev_rec, uint32_t n, uint32_t T, uint32_t stride,
+                             const tsw_point *starts, const tsw_task *tasks, const uint32_t *release,
+                             uint32_t m, uint32_t rule, tsw_timeline *sum, uint32_t *task);
+/* Measurement probe (not part of the reference interface): the last timeline call of the context. out[0..2] =
+ * ms of the passes A (events), B (replay) and C (attach), HIP-event timed on the context stream (0 with timing
+ * off); out[3] = takes replayed; out[4] = candidates scanned by the takes' arg-min, summed. */
+int tsw_probe_timeline(const tsw_ctx *ctx, double *out);
 
 /* K1: BFS distance tables for k goal cells, u16 per cell, row-major
  * (TSW_DIST_INF for blocked/unreachable). out: host buffer k*w*h. */

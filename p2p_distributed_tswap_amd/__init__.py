@@ -43,6 +43,9 @@ TSW_ACT_MOVE, TSW_ACT_GOAL_SWAP, TSW_ACT_ROTATION, TSW_ACT_WAIT = 0, 1, 2, 3
 # tsw_audit_records (include/tswap.h): words per column / per agent, violation kinds
 TSW_AUDIT_NCOL, TSW_AUDIT_NAGENT, TSW_AUDIT_NKIND = 11, 4, 5
 AUDIT_KINDS = ("colocation", "swap", "jump", "off_map", "bad_state")
+# tsw_task_timeline (include/tswap.h): dispatch rules, words per task
+TSW_TL_NEAREST, TSW_TL_STREAM, TSW_TL_NTASK = 0, 1, 4
+TIMELINE_RULES = {"nearest": TSW_TL_NEAREST, "stream": TSW_TL_STREAM}
 DIST_INF = 0xFFFF
 
 
@@ -136,6 +139,20 @@ class Audit(ctypes.Structure):
         return d
 
 
+class Timeline(ctypes.Structure):
+    """tsw_timeline (include/tswap.h)."""
+    _fields_ = [
+        ("wait_sum", ctypes.c_uint64), ("service_sum", ctypes.c_uint64), ("carry_sum", ctypes.c_uint64),
+        ("assigned", ctypes.c_uint32), ("carried", ctypes.c_uint32), ("delivered", ctypes.c_uint32),
+        ("unreleased", ctypes.c_uint32), ("service_min", ctypes.c_uint32), ("service_max", ctypes.c_uint32),
+        ("makespan", ctypes.c_uint32), ("consistent", ctypes.c_uint32), ("bad_kind", ctypes.c_uint32),
+        ("bad_t", ctypes.c_uint32), ("bad_agent", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol declared in include/tswap.h (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
     "tsw_create", "tsw_destroy", "tsw_last_error", "tsw_plan_mapd", "tsw_plan_mapd_trace",
@@ -145,6 +162,7 @@ EXPORTED_SYMBOLS = (
     "tsw_abi_version", "tsw_plan_mapd_resolved", "tsw_next_hop_codes", "tsw_build_id",
     "tsw_host_next_hop_codes", "tsw_nearby", "tsw_decide_fleet", "tsw_fleet_apply", "tsw_fleet_run",
     "tsw_fleet_mapd", "tsw_audit_records", "tsw_audit_records_device", "tsw_plan_mapd_online",
+    "tsw_task_timeline", "tsw_task_timeline_device", "tsw_probe_timeline",
 )
 
 # tsw_resolve_fn (include/tswap.h): int (*)(void *user, uint32_t k, const uint32_t *start,
@@ -203,6 +221,14 @@ def load_library(path: str = LIB_PATH):
     lib.tsw_audit_records.restype = ctypes.c_int
     lib.tsw_audit_records_device.argtypes = [vp, vp, u32, u32, u32, P(Audit), P(u32), P(u32)]
     lib.tsw_audit_records_device.restype = ctypes.c_int
+    lib.tsw_task_timeline.argtypes = [vp, P(_Rec), u32, u32, u32, P(_Point), P(_Task), P(u32), u32, u32, P(Timeline),
+                                      P(u32)]
+    lib.tsw_task_timeline.restype = ctypes.c_int
+    lib.tsw_task_timeline_device.argtypes = [vp, vp, u32, u32, u32, P(_Point), P(_Task), P(u32), u32, u32, P(Timeline),
+                                             P(u32)]
+    lib.tsw_task_timeline_device.restype = ctypes.c_int
+    lib.tsw_probe_timeline.argtypes = [vp, P(ctypes.c_double)]
+    lib.tsw_probe_timeline.restype = ctypes.c_int
     lib.tsw_dist_tables.argtypes = [vp, P(u32), u32, P(ctypes.c_uint16)]
     lib.tsw_dist_tables_device.argtypes = [vp, P(u32), u32, vp]
     lib.tsw_import_tables_device.argtypes = [vp, P(u32), u32, vp]
@@ -615,6 +641,63 @@ class Planner:
         torch int64 tensor's data_ptr), agent i's column t at ptr + 8 * (i * stride + t)."""
         return self._audit(lambda s, c, a: self._lib.tsw_audit_records_device(self._ctx, ptr, n, T, stride, s, c, a),
                            int(n), int(T), col, agents)
+
+    # --- task timeline ------------------------------------------------------
+    def _timeline(self, call, starts_xy, tasks_xyxy, release, rule):
+        if rule not in TIMELINE_RULES:
+            raise TswapError(TSW_EINVAL, f"rule must be one of {sorted(TIMELINE_RULES)}")
+        tasks = np.ascontiguousarray(tasks_xyxy, dtype=np.uint32).reshape(-1, 4)
+        m = tasks.shape[0]
+        starts = None if starts_xy is None else np.ascontiguousarray(starts_xy, dtype=np.uint32).reshape(-1, 2)
+        rel = None
+        if release is not None:
+            rel = np.ascontiguousarray(release, dtype=np.uint32).reshape(-1)
+            if rel.size != m:
+                raise TswapError(TSW_EINVAL, "release must hold one time per task")
+        sm = Timeline()
+        tw = np.full((m, TSW_TL_NTASK), 0xFFFFFFFF, dtype=np.uint32)
+        self._check(call(starts.ctypes.data_as(ctypes.POINTER(_Point)) if starts is not None and starts.size else None,
+                         tasks.ctypes.data_as(ctypes.POINTER(_Task)) if m else None,
+                         _u32p(rel) if rel is not None else None, m, TIMELINE_RULES[rule], ctypes.byref(sm),
+                         _u32p(tw) if m else None))
+        out = sm.as_dict()
+        out["task"] = tw
+        return out
+
+    def task_timeline(self, rec, starts_xy, tasks_xyxy, release=None, rule: str = "nearest") -> dict:
+        """tsw_task_timeline: which agent took each task and when it was assigned, picked up and delivered,
+        replayed on the device from plan records alone. rec: the packed (n, T) uint64 array plan_mapd_arrays,
+        plan_mapd_online and fleet_mapd return, or any prefix of its columns; starts_xy, tasks_xyxy, release:
+        what that plan call was given. rule: "nearest" for the centralized plans, "stream" for fleet_mapd
+        (release must be None; starts_xy may be). Returns tsw_timeline's fields (wait_sum, service_sum,
+        carry_sum, assigned, carried, delivered, unreleased, service_min, service_max, makespan, consistent,
+        bad_kind, bad_t, bad_agent) plus "task", an (m, 4) uint32 array of agent, t_assign, t_carry, t_deliver
+        (0xFFFFFFFF: did not happen)."""
+        rec = np.ascontiguousarray(rec, dtype=np.uint64)
+        if rec.ndim != 2:
+            raise TswapError(TSW_EINVAL, "rec must be an (n, T) array")
+        n, T = rec.shape
+        if starts_xy is not None and np.asarray(starts_xy).size != 2 * n:
+            raise TswapError(TSW_EINVAL, "starts_xy must hold one point per row of rec")
+        rp = rec.ctypes.data_as(ctypes.POINTER(_Rec))
+        return self._timeline(lambda *a: self._lib.tsw_task_timeline(self._ctx, rp, n, T, T, *a),
+                              starts_xy, tasks_xyxy, release, rule)
+
+    def task_timeline_device(self, ptr: int, n: int, T: int, stride: int, starts_xy, tasks_xyxy, release=None,
+                             rule: str = "nearest") -> dict:
+        """tsw_task_timeline_device: as task_timeline, the records in device memory on the context's device
+        (e.g. a torch int64 tensor's data_ptr), agent i's column t at ptr + 8 * (i * stride + t)."""
+        if starts_xy is not None and np.asarray(starts_xy).size != 2 * int(n):
+            raise TswapError(TSW_EINVAL, "starts_xy must hold one point per agent")
+        return self._timeline(lambda *a: self._lib.tsw_task_timeline_device(self._ctx, ptr, int(n), int(T), int(stride), *a),
+                              starts_xy, tasks_xyxy, release, rule)
+
+    def timeline_probe(self) -> dict:
+        """tsw_probe_timeline: the last timeline call's kernel times per pass (ms) and its replay counters."""
+        out = (ctypes.c_double * 5)()
+        self._check(self._lib.tsw_probe_timeline(self._ctx, out))
+        return {"events_ms": out[0], "replay_ms": out[1], "attach_ms": out[2], "takes": int(out[3]),
+                "candidates_scanned": int(out[4])}
 
     # --- get_path -----------------------------------------------------------
     def get_path_next(self, start: np.ndarray, goal: np.ndarray):

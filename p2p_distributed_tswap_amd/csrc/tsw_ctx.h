@@ -271,6 +271,12 @@ struct tsw_ctx {
   DevBuf<unsigned long long> d_aud_rec;
   DevBuf<uint32_t> d_aud_cid, d_aud_out;
   DevBuf<unsigned long long> d_aud_tab;
+  // tsw_task_timeline scratch (grow-only): pass A's event table (T * n bytes) and every word array of a
+  // call in one block (timeline_device, tsw_timeline_host.hip, lays it out); records that come from the host
+  // go up into d_aud_rec, the audit's. tl_last: what tsw_probe_timeline reports of the last call.
+  DevBuf<uint8_t> d_tl_ev;
+  DevBuf<uint32_t> d_tl_w;
+  double tl_last[5] = {};
 
   // stats / timing
   tsw_stats st{};
@@ -393,6 +399,13 @@ int grow_synced(tsw_ctx* c, DevBuf<T>& b, size_t need) {
   HIPCHK(hipStreamSynchronize(c->s));
   HIPCHK(b.grow(need));
   return TSW_OK;
+}
+
+// The pickup point the nearest-pickup choice measures to, x | y << 16: the raw point with its coordinates
+// clamped to 0xFFFE (plan_validate_index says why that cannot change the winner). tsw_task_timeline replays
+// the choice from the same word.
+inline uint32_t task_pxy(const tsw_task& t) {
+  return std::min<uint32_t>(t.pickup.x, 0xFFFEu) | (std::min<uint32_t>(t.pickup.y, 0xFFFEu) << 16);
 }
 
 // Morton (Z-order) key of a point: the low 16 bits of x and y interleaved, x in the even bits.

@@ -7,6 +7,7 @@
 //   planner   plan_lds_bytes, choose_plan_placement, plan_variant   (k_plan, tsw_plan_kernel.h)
 //   workers   worker_config, worker_layout, the k_astar_wave sizes  (tsw_worker.h, tsw_astar.hip)
 //   K1        the five kernels' carve sizes and fit tests, choose_bfs (tsw_bfs*.hip, run_bfs)
+//   K8        the task timeline's tiles, workgroups and LDS share     (tsw_timeline.hip)
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -413,5 +414,27 @@ inline BfsChoice choose_bfs(const BfsGeom& g, const BfsKnobs& t, int max_lds, in
   return BfsChoice{BFS_BLOCK, bfs_lds_bytes(g.H, (g.W + 31u) / 32u, g.ncell, false) <= (size_t)std::max(max_lds, 0),
                    0u, false, 0u};
 }
+
+// ---- K8: the task timeline's three passes (tsw_timeline.hip) ----------------------------------------
+// Pass A works on tiles of TL_TILE_AGENTS agents x TL_TILE_COLS columns, one TL_A_BLOCK-thread workgroup
+// each. Pass B is one workgroup of TL_B_BLOCK threads, whatever the instance: the replay is sequential in
+// (t, agent), and a take's arg-min wants every lane of one CU. Its candidates (8 B a task) go to dynamic LDS
+// as far as the workgroup's limit allows beside the static tl_replay_lds_bytes, in whole strides of the
+// block (tl_lds_candidates: 18,432 of them with 160 KiB); the others stay in global memory. Pass C is one
+// thread per task.
+constexpr uint32_t TL_TILE_AGENTS = 64u, TL_TILE_COLS = 64u, TL_A_BLOCK = 256u;
+constexpr uint32_t TL_B_BLOCK = 1024u, TL_C_BLOCK = 256u;
+// pass B's LDS: release counts and flags of TL_B_BLOCK columns, the takers' positions of TL_B_BLOCK agents,
+// and per wave the take mask, the stay mask and the arg-min slot
+constexpr size_t tl_replay_lds_bytes() { return (size_t)TL_B_BLOCK * 4u * 3u + (size_t)(TL_B_BLOCK / 64u) * 8u * 3u; }
+inline uint32_t tl_tiles(uint32_t count, uint32_t tile) { return (count + tile - 1u) / tile; }
+// candidates of pass B that live in LDS: a multiple of TL_B_BLOCK, no more than m rounded up to one
+inline uint32_t tl_lds_candidates(uint32_t m, int max_lds) {
+  const size_t fixed = tl_replay_lds_bytes() + 1024u;  // the static part and some room for the compiler's own
+  if (max_lds <= 0 || (size_t)max_lds <= fixed) return 0u;
+  const size_t fit = ((size_t)max_lds - fixed) / 8u / TL_B_BLOCK, want = ((size_t)m + TL_B_BLOCK - 1u) / TL_B_BLOCK;
+  return (uint32_t)(std::min(fit, want) * TL_B_BLOCK);
+}
+inline uint32_t tl_attach_workgroups(uint32_t m) { return std::max<uint32_t>(tl_tiles(m, TL_C_BLOCK), 1u); }
 
 }  // namespace tsw

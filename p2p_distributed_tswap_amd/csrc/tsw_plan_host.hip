@@ -812,7 +812,7 @@ int plan_validate_index(tsw_ctx* c, const tsw_point* starts, uint32_t n, const t
   for (uint32_t k = 0; k < m; ++k) {
     if (!cell_ok(c, tasks[k].pickup.x, tasks[k].pickup.y, &pick[k])) pick[k] = CELL_BAD;
     if (!cell_ok(c, tasks[k].delivery.x, tasks[k].delivery.y, &dlv[k])) dlv[k] = CELL_BAD;
-    pxy[k] = std::min<uint32_t>(tasks[k].pickup.x, 0xFFFEu) | (std::min<uint32_t>(tasks[k].pickup.y, 0xFFFEu) << 16);
+    pxy[k] = task_pxy(tasks[k]);
     if (pick[k] != CELL_BAD) goalset.push_back(pick[k]);
     if (dlv[k] != CELL_BAD) goalset.push_back(dlv[k]);
   }

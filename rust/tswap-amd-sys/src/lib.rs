@@ -60,6 +60,11 @@ pub const TSW_AUDIT_NCOL: u32 = 11;
 pub const TSW_AUDIT_NAGENT: u32 = 4;
 pub const TSW_AUDIT_NKIND: u32 = 5;
 
+/// `tsw_task_timeline`'s dispatch rules and the words per task of its `task` table.
+pub const TSW_TL_NEAREST: u32 = 0;
+pub const TSW_TL_STREAM: u32 = 1;
+pub const TSW_TL_NTASK: u32 = 4;
+
 /// `tsw_resolve_fn`: the caller's K3 for `tsw_plan_mapd_resolved` — fill `code[i]` (0..3 S,E,N,W,
 /// 4 stay) for get_path(start[i], goal[i]) and return 0 (e.g. send each pair to its goal's owner).
 pub type TswResolveFn =
@@ -100,6 +105,28 @@ pub struct TswAudit {
     pub moving_columns: u32,
     pub first_t: [u32; 5],
     pub first_agent: [u32; 5],
+}
+
+/// `tsw_timeline`: the summary of `tsw_task_timeline` (times in steps; `TaskMetric`'s sent_time is the
+/// release, start_time is t_assign, completion_time is t_deliver). `consistent == 0`: the records
+/// contradict the dispatch rule at (`bad_t`, `bad_agent`), and the sums hold the events before it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct TswTimeline {
+    pub wait_sum: u64,
+    pub service_sum: u64,
+    pub carry_sum: u64,
+    pub assigned: u32,
+    pub carried: u32,
+    pub delivered: u32,
+    pub unreleased: u32,
+    pub service_min: u32,
+    pub service_max: u32,
+    pub makespan: u32,
+    pub consistent: u32,
+    pub bad_kind: u32,
+    pub bad_t: u32,
+    pub bad_agent: u32,
 }
 
 #[repr(C)]
@@ -202,6 +229,15 @@ extern "C" {
                              col: *mut u32, agent: *mut u32) -> c_int;
     pub fn tsw_audit_records_device(ctx: *mut TswCtx, dev_rec: *const TswRec, n: u32, t: u32, stride: u32,
                                     sum: *mut TswAudit, col: *mut u32, agent: *mut u32) -> c_int;
+    /// Per-task agent, t_assign, t_carry, t_deliver (`task`: m * TSW_TL_NTASK words, may be null) and the
+    /// summary, replayed from plan records on the device; `release` null: every task at 0.
+    pub fn tsw_task_timeline(ctx: *mut TswCtx, rec: *const TswRec, n: u32, t: u32, stride: u32,
+                             starts: *const TswPoint, tasks: *const TswTask, release: *const u32, m: u32,
+                             rule: u32, sum: *mut TswTimeline, task: *mut u32) -> c_int;
+    pub fn tsw_task_timeline_device(ctx: *mut TswCtx, dev_rec: *const TswRec, n: u32, t: u32, stride: u32,
+                                    starts: *const TswPoint, tasks: *const TswTask, release: *const u32, m: u32,
+                                    rule: u32, sum: *mut TswTimeline, task: *mut u32) -> c_int;
+    pub fn tsw_probe_timeline(ctx: *const TswCtx, out: *mut f64) -> c_int;
     pub fn tsw_dist_tables(ctx: *mut TswCtx, goals: *const u32, k: u32, out: *mut u16) -> c_int;
     pub fn tsw_dist_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_out: *mut u16) -> c_int;
     pub fn tsw_import_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_tables: *const u16) -> c_int;
