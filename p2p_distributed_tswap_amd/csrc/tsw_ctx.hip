@@ -69,6 +69,7 @@ Tunables Tunables::from_env() {
   t.prefetch_ext = (uint32_t)num("TSW_PREFETCH_EXT", 0, 7, t.prefetch_ext);
   t.flinks_lds = getenv("TSW_NO_FLINKS_LDS") == nullptr;
   t.part_lds = (uint32_t)num("TSW_PART_LDS", 0, 0x7F, t.part_lds);
+  t.agents_lds = num("TSW_AGENTS_LDS", 0, 1, 1) != 0;
   t.occ_split = num("TSW_OCC_SPLIT", 0, 1, 1) != 0;
   t.plan_block = (uint32_t)num("TSW_PLAN_BLOCK", 0, PLAN_BLOCK_MAX, 0) / 64u * 64u;
   t.plan_debug = getenv("TSW_PLAN_DEBUG") != nullptr;

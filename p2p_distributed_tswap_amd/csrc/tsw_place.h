@@ -67,11 +67,12 @@ inline size_t plan_lds_bytes(uint32_t n, uint32_t ncell, uint32_t m, const PlanP
 }
 
 // What of the planner's state lives in LDS, in priority order: agents, occupancy grid, task table.
-// part_mask / flinks_on / occ_split: Tunables::part_lds / flinks_lds / occ_split.
+// part_mask / flinks_on / occ_split / agents_on: Tunables::part_lds / flinks_lds / occ_split / agents_lds
+// (agents_on false: the whole set stays out of LDS however small the fleet — diagnostic builds only).
 inline PlanPlacement choose_plan_placement(uint32_t n, uint32_t ncell, uint32_t m, int max_lds, uint32_t part_mask,
-                                           bool flinks_on, bool occ_split) {
+                                           bool flinks_on, bool occ_split, bool agents_on = true) {
   const size_t budget = (size_t)std::max(max_lds - PLAN_LDS_RESERVE, 0);
-  bool ag = plan_lds_bytes(n, ncell, m, true, false, false) <= budget;
+  bool ag = agents_on && plan_lds_bytes(n, ncell, m, true, false, false) <= budget;
   // without the whole set, single agent arrays in priority order (PART_*: the rules phase's serial
   // successor walks and firing scans read SUCC / ONC / V / G; wh10k rules 3.9 -> ? s), then the rules
   // relabel's pointer-doubling buffers

@@ -73,7 +73,8 @@ static T* per_agent(tsw_ctx* c, DevBuf<T>& b, uint32_t n, int fill) {
 // What of the planner's state lives in LDS (choose_plan_placement, tsw_place.h), into PlanArgs.
 static void choose_plan_lds(const tsw_ctx* c, PlanArgs* P) {
   const PlanPlacement pl =
-      choose_plan_placement(P->n, P->ncell, P->m, c->max_lds, c->tun.part_lds, c->tun.flinks_lds, c->tun.occ_split);
+      choose_plan_placement(P->n, P->ncell, P->m, c->max_lds, c->tun.part_lds, c->tun.flinks_lds, c->tun.occ_split,
+                            c->tun.agents_lds);
   P->part_lds = pl.part, P->f_lds = pl.flinks, P->mu_lds = pl.mu;
   P->agents_lds = pl.agents, P->occ_lds = pl.occ, P->tasks_lds = pl.tasks;
 }
@@ -580,6 +581,9 @@ static int run_plan_impl(tsw_ctx* c, PlanArgs& P, Dispatch& D, bool setup, const
   TRY(upload_ctl(c, init));
   if (setup) TRY(setup_dispatch(c, P, &D));
   uint64_t bound = 16ull * P.n + 4096ull * (init.max_t + 1);  // launches without reaching the end
+  // PlanCtl's relabel counters run on through the relaunches of a call (and the segments of an online plan): the
+  // stats take each launch's increase, not its running total
+  uint32_t full0 = init.relabel_full, inc0 = init.relabel_inc;
   for (uint64_t launches = 0;;) {
     if (launches > bound) RET(TSW_EINVAL, "plan kernel made no progress");
     const bool coop = P.coop != 0;
@@ -598,8 +602,9 @@ static int run_plan_impl(tsw_ctx* c, PlanArgs& P, Dispatch& D, bool setup, const
     if (coop) TRY(harvest_coop(c, D.W));
     const PlanCtl k = *c->h_ctl;
     TRY(plan_error(c, k));
-    c->st.relabels_full += k.relabel_full;
-    c->st.relabels_inc += k.relabel_inc;
+    c->st.relabels_full += k.relabel_full - full0;
+    c->st.relabels_inc += k.relabel_inc - inc0;
+    full0 = k.relabel_full, inc0 = k.relabel_inc;
     if (k.status == PLAN_DONE) {
       c->chase_id = k.chase_id;
       c->st.rule_rounds += k.rule_rounds;

@@ -603,7 +603,8 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
         s_ctl.rule_rounds += 1;
         return o;
       };
-      // n <= 512: wave 0 alone runs scan + fire rounds back to back — the scan is a ballot over
+      // n <= P.wave_rules_max (every n by default: Tunables::wave_rules_max is 0xFFFFFFFF): wave 0
+      // alone runs scan + fire rounds back to back — the scan is a ballot over
       // 64 agents from the cursor, the fire is lane 0 of the same wave, so a round needs no
       // workgroup barrier and no cross-wave reduction; the block joins only when a firing
       // changed next hops (refresh + relabel) or the phase ends.
@@ -947,7 +948,10 @@ __global__ void __launch_bounds__(PLAN_BLOCK_MAX) k_plan(const PlanArgs* __restr
                 prof(TK_WB_APPLY);
                 // an empty batch (lane l's own walk closed a cycle or ran long): lane l fires on the serial path
                 if (batch != 0ull) {
-                  if (kdbg && lane == 0) s_tick[TK_R4_ROTATIONS] += (uint32_t)__popcll(__ballot(inb && r2));  // rule-4 rotations
+                  if (kdbg) {  // diagnostics: rule-4 rotations of the batch (the ballot needs every lane, not lane 0 alone)
+                    const uint32_t nrot = (uint32_t)__popcll(__ballot(inb && r2));
+                    if (lane == 0) s_tick[TK_R4_ROTATIONS] += nrot;
+                  }
                   if (touched && k < n) {  // exact state after the batch, from LDS
                     sk = S.SUCC[k];
                     onck = S.ONC[k] != 0;

@@ -75,6 +75,46 @@ static void planner_pins() {
     CHECK(plan_variant(p) == r.variant, "n %u %ux%u mask 0x%x: variant %d, recorded %d", r.n, r.W, r.H, r.mask,
           plan_variant(p), r.variant);
   }
+  // the last parameter (agents_on, Tunables::agents_lds) defaults to true: leaving it out and passing true give every
+  // recorded placement above
+  auto same = [](const PlanPlacement& a, const PlanPlacement& b) {
+    return a.agents == b.agents && a.occ == b.occ && a.mu == b.mu && a.flinks == b.flinks && a.tasks == b.tasks && a.part == b.part;
+  };
+  for (const Row& r : rows) {
+    const PlanPlacement d = choose_plan_placement(r.n, r.W * r.H, 0u, MI355X_LDS, r.mask, true, true);
+    const PlanPlacement t = choose_plan_placement(r.n, r.W * r.H, 0u, MI355X_LDS, r.mask, true, true, true);
+    CHECK(same(d, t) && plan_variant(t) == r.variant, "n %u %ux%u mask 0x%x: agents_on = true gives variant %d, the default %d",
+          r.n, r.W, r.H, r.mask, plan_variant(t), plan_variant(d));
+  }
+  // the three placements of tests/test_gpu_rules.py, at the fleets and grids of tests/rules_cases.py:
+  //   ag      no knob                                   -> k_plan<true, true, true, false>   (0)
+  //   global  TSW_AGENTS_LDS=0 TSW_PART_LDS=0x7F        -> k_plan<false, true, true, false>  (4): the arrays admitted one by one
+  //   pg      TSW_AGENTS_LDS=0 TSW_PART_LDS=0x3F, a case in the corner of a blocked 208x208 map: 43,264 cells x 4 B of OCC
+  //           do not fit beside the parts                -> k_plan<false, false, false, true> (3)
+  struct Small {
+    uint32_t n, W, H;
+  };
+  // every (fleet, grid) of tests/rules_cases.py. tests/test_rules_cases.py::test_place_rows_cover_every_case reads this
+  // initialiser and the `for (uint32_t n : {` list below from the source text: keep the two literals' form when editing
+  const Small small[] = {{2, 64, 1},     {4, 2, 2},      {10, 4, 3},     {16, 16, 1},    {16, 40, 24},   {17, 17, 1},   {17, 19, 1},
+                         {18, 18, 1},    {18, 20, 1},    {19, 21, 1},    {21, 40, 24},   {22, 64, 6},    {60, 14, 10},  {62, 17, 16},
+                         {62, 64, 3},    {63, 14, 10},   {64, 17, 17},   {64, 64, 1},    {64, 64, 3},    {65, 65, 1},   {66, 18, 17},
+                         {66, 64, 5},    {66, 66, 1},    {69, 14, 10},   {71, 80, 24},   {128, 33, 33},  {131, 131, 1}, {248, 34, 34},
+                         {1024, 64, 63}, {1026, 64, 65}, {1088, 64, 22}, {1088, 64, 36}};
+  for (const Small& c : small) {
+    const PlanPlacement ag = choose_plan_placement(c.n, c.W * c.H, 0u, MI355X_LDS, 0x7Fu, true, true);
+    CHECK(ag.agents && ag.part == 0u && plan_variant(ag) == 0, "ag, n %u %ux%u: variant %d", c.n, c.W, c.H, plan_variant(ag));
+    const PlanPlacement gl = choose_plan_placement(c.n, c.W * c.H, 0u, MI355X_LDS, 0x7Fu, true, true, false);
+    CHECK(!gl.agents && gl.part == 0x7Fu && gl.flinks && gl.occ && gl.mu && plan_variant(gl) == 4,
+          "global, n %u %ux%u: part 0x%x occ %d mu %d variant %d", c.n, c.W, c.H, gl.part, gl.occ, gl.mu, plan_variant(gl));
+  }
+  for (uint32_t n : {4u, 10u, 22u, 62u, 64u, 66u, 128u, 1088u}) {
+    const PlanPlacement pg = choose_plan_placement(n, 208u * 208u, 0u, MI355X_LDS, 0x3Fu, true, true, false);
+    CHECK(!pg.agents && pg.part == PART_PG && pg.flinks && !pg.occ && !pg.mu && plan_variant(pg) == 3,
+          "pg, n %u on 208x208: part 0x%x occ %d variant %d", n, pg.part, pg.occ, plan_variant(pg));
+    // with the agent arrays allowed in LDS the same fleet is an AG placement: the knob alone reaches PG at this size
+    CHECK(choose_plan_placement(n, 208u * 208u, 0u, MI355X_LDS, 0x3Fu, true, true).agents, "n %u on 208x208 without the knob", n);
+  }
   CHECK(plan_lds_bytes(400, 170 * 84, 0, true, true, false) == 4096u + 12848u + 114240u, "the first row by hand");
   CHECK(MI355X_LDS - PLAN_LDS_RESERVE == 161792, "budget");
 }
@@ -162,6 +202,13 @@ static void sweep_planner() {
             for (int sp = 0; sp < 2; ++sp) {
               const uint32_t ncell = g.W * g.H;
               const PlanPlacement p = choose_plan_placement(n, ncell, 3u * n, max_lds, mask, fl != 0, sp != 0);
+              // agents_on: true is the default; false never places the whole set and still fits
+              const PlanPlacement pt = choose_plan_placement(n, ncell, 3u * n, max_lds, mask, fl != 0, sp != 0, true);
+              const PlanPlacement pf = choose_plan_placement(n, ncell, 3u * n, max_lds, mask, fl != 0, sp != 0, false);
+              CHECK(pt.agents == p.agents && pt.part == p.part && pt.occ == p.occ && pt.mu == p.mu && pt.flinks == p.flinks,
+                    "n %u %ux%u: agents_on = true differs from the default", n, g.W, g.H);
+              CHECK(!pf.agents && (pf.part & ~mask) == 0u && plan_lds_bytes(n, ncell, 3u * n, pf) <= (size_t)(max_lds - PLAN_LDS_RESERVE),
+                    "n %u %ux%u mask 0x%x, agents_on = false: agents %d part 0x%x", n, g.W, g.H, mask, pf.agents, pf.part);
               const size_t budget = (size_t)(max_lds - PLAN_LDS_RESERVE);
               const int v = plan_variant(p);
               CHECK(plan_lds_bytes(n, ncell, 3u * n, p) <= budget, "n %u %ux%u lds %d mask 0x%x: %zu B over %zu", n, g.W, g.H,

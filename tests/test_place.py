@@ -3,7 +3,9 @@ UndefinedBehaviorSanitizer (tests/host/place_main.cpp, host compiler, no HIP and
 placement (six flags, k_plan instantiation, LDS bytes) of every parity case that profiles/r16/gpu_tests.txt and
 profiles/r17/placement_parent.txt record from an MI355X, all seven instantiations among them; the worker layouts of C3,
 wh10k and C5 (1,020 / 1,275 / 2,295 waves); den520d -> k_bfs_blk, 1024x1024 -> k_bfs_big, the 2048x33 grid that does
-not fit k_bfs_mg (169,412 B); the 16-byte bitmap padding on 200x130. Swept over grids from 1x1 to the 2^20-cell and
+not fit k_bfs_mg (169,412 B); the 16-byte bitmap padding on 200x130. The last parameter of choose_plan_placement
+(agents_on, TSW_AGENTS_LDS) left out gives every recorded placement; the three placements of tests/test_gpu_rules.py (ag,
+global, pg) at the fleets and grids of tests/rules_cases.py. Swept over grids from 1x1 to the 2^20-cell and
 2048-side limits, 1 .. 65,535 agents, 64 and 160 KiB of LDS, 1 and 256 CUs: a placement fits its budget, mu implies occ
 and 16-bit agent ids, every placement has an instantiation; a worker layout fits the dispatch's LDS and keeps the staged
 bitmap beside LDS g-scores; a K1 choice fits, a forced kernel that does not reports itself, the default mode always has
