@@ -69,7 +69,9 @@ extern "C" {
  * tsw_fleet_run, and after them tsw_fleet_mapd, were added without touching a struct or an existing
  * signature, and so were tsw_audit_records and tsw_audit_records_device (one new struct, tsw_audit), and
  * then tsw_plan_mapd_online (no struct, no existing signature touched), and then tsw_task_timeline,
- * tsw_task_timeline_device and tsw_probe_timeline (one new struct, tsw_timeline); a
+ * tsw_task_timeline_device and tsw_probe_timeline (one new struct, tsw_timeline), and then
+ * tsw_astar_reserved, tsw_host_astar_reserved and tsw_probe_st_astar (two new structs, tsw_node_res and
+ * tsw_edge_res); a
  * caller that wants them looks the symbols up (dlsym) instead of comparing the revision. */
 #define TSW_ABI_VERSION 8
 
@@ -485,6 +487,75 @@ int tsw_task_timeline_device(tsw_ctx *ctx, const tsw_rec *dev_rec, uint32_t n, u
  * ms of the passes A (events), B (replay) and C (attach), HIP-event timed on the context stream (0 with timing
  * off); out[3] = takes replayed; out[4] = candidates scanned by the takes' arg-min, summed. */
 int tsw_probe_timeline(const tsw_ctx *ctx, double *out);
+
+/* K9: astar_with_reservation (src/algorithm/a_star.rs:32-112), batched: k space-time A* searches over
+ * (cell, time) with WAIT moves that avoid reserved vertices (cell, t) and edges ((from, to), t). Query i is
+ * (start[i], goal[i], start_time[i]), cell ids of free cells. This is the primitive only: a prioritised planner
+ * (agents in sequence, each reserving its path) is not in the reference and not in this library.
+ * Search. The open set is a BinaryHeap of TimeNode {pos, g, f}, g the time, f = g + Manhattan(pos, goal), ordered
+ * by a_star.rs:15-19 (smaller f first, then smaller g; pos takes no part) — AstarNode's order, restated once
+ * for the whole library. (start, start_time) is pushed first and is not checked against the reservations. A
+ * popped node at the goal ends the search: the path is its came_from chain. Otherwise its successors are
+ * generated in the order (dx, dy) = (1,0), (-1,0), (0,1), (0,-1), (0,0) — x the column, y the row, the last
+ * one WAIT — with np the successor cell and nt = g + 1, and one is skipped when
+ *   np is off the grid or blocked ('@'), or (np, nt) is a reserved vertex, or (pos, nt) is a reserved vertex
+ *   (a reserved current cell forbids leaving it too: the reference's rule), or ((pos, np), nt) or ((np, pos), nt)
+ *   is a reserved edge (WAIT: ((pos, pos), nt)), or the state (np, nt) was pushed before;
+ * every other one records came_from[(np, nt)] = (pos, g) and is pushed. Every state is pushed at most once.
+ * Where the reference is replaced. (1) It bounds the grid by its compile-time 100 x 100 and takes every byte
+ * but '.' as blocked; here the bounds are the context's w, h and blocked is '@' — identical on maps of '.' and
+ * '@'. (2) It never returns when the goal cannot be reached (WAIT makes the state space infinite). Two caps,
+ * both at points where they cannot change a path that is found: a popped node with f > max_time stops the
+ * search with TSW_SP_NONE (pushes are never filtered by time, so the heap — and the tie-break — is the
+ * reference's up to that pop, and any path that arrives by max_time is the reference's); a push that would be
+ * the (max_nodes + 1)-th of the query, the start included, stops it with TSW_SP_CAPACITY. An emptied heap (the
+ * start boxed in) is the reference's None: TSW_SP_NONE.
+ * Outputs, CSR: query i's path is path[path_off[i] .. path_off[i+1]) as cell ids, entry j the cell at time
+ * start_time[i] + j, the first one start[i]; empty unless status[i] == TSW_SP_FOUND. path_off[k+1] and *total =
+ * path_off[k] are always written. *total > path_cap: TSW_EOVERFLOW with path_off, status, pops and *total valid
+ * and path untouched (path may be NULL with path_cap 0: a size query). pops (may be NULL): pops[i] = nodes
+ * popped with f <= max_time, the goal's pop included.
+ * TSW_EINVAL before anything is launched, the outputs untouched: a start or goal off the grid or blocked;
+ * max_time > 2^20; a start_time[i] > 2^20; max_nodes == 0; a NULL array whose count is not 0 (start, goal,
+ * start_time, path_off, status, total with k > 0; node_res / edge_res with n_node / n_edge > 0; path with
+ * path_cap > 0); a context inside its own resolver. start_time[i] + Manhattan > max_time is no error:
+ * TSW_SP_NONE with 0 pops. Reservation entries may repeat and may name off-grid cells, non-adjacent pairs or
+ * times past the horizon: legal, never matched. k == 0: TSW_OK with path_off[0] = 0 and *total = 0. TSW_ENOMEM
+ * when the scratch of even one query does not fit (8 bytes per visited-table slot, 2 * max_nodes slots
+ * rounded up to a power of two, and 8 bytes per node of the overflow heap, max_nodes taken as at most
+ * w * h * (max_time + 2), the number of states a search can push); otherwise the queries run
+ * in as many batches as the free memory needs. A reservation list of more than 2^30 keys, or a visited table of
+ * more than 2^31 slots, is TSW_ENOMEM too. The scratch is grow-only and stays with the context until it is
+ * destroyed: one table and one overflow heap per search wave in flight, at most min(k, 32 waves per CU) of
+ * them and at most half of the free memory or 16 GiB — with the default max_nodes of 65,536 that is 1.5 MiB a
+ * wave, 12 GiB for a call of 8,192 or more queries on a 256-CU device (wiped once, on the first call of that
+ * size); a smaller max_nodes shrinks it in proportion. The call reads the grid only: the table store, the queues and
+ * the stats stay as they were, and a plan after it equals a plan without it. */
+typedef struct { uint32_t cell, t; } tsw_node_res;         /* (Point, time)            */
+typedef struct { uint32_t from, to, t; } tsw_edge_res;     /* ((Point, Point), time)   */
+#define TSW_SP_FOUND 0u
+#define TSW_SP_NONE 1u
+#define TSW_SP_CAPACITY 2u
+int tsw_astar_reserved(tsw_ctx *ctx, const uint32_t *start, const uint32_t *goal, const uint32_t *start_time,
+                       uint32_t k, const tsw_node_res *node_res, uint32_t n_node,
+                       const tsw_edge_res *edge_res, uint32_t n_edge, uint32_t max_time, uint32_t max_nodes,
+                       uint32_t *path_off, uint32_t *path, uint32_t path_cap, uint32_t *status,
+                       uint32_t *pops, uint32_t *total);
+/* The same search in plain C++ on the calling thread — no context and no device: cells as for the context's
+ * creation (h rows of w bytes; TSW_EINVAL for a bad grid), every other argument and every output as above.
+ * The serial form the device must equal and the CPU baseline it is measured against; it shares the reservation
+ * set, the visited table and the heap order with the kernel, so the independent check of both is the test
+ * suite's model. */
+int tsw_host_astar_reserved(const uint8_t *cells, uint32_t w, uint32_t h, const uint32_t *start,
+                            const uint32_t *goal, const uint32_t *start_time, uint32_t k,
+                            const tsw_node_res *node_res, uint32_t n_node, const tsw_edge_res *edge_res,
+                            uint32_t n_edge, uint32_t max_time, uint32_t max_nodes, uint32_t *path_off,
+                            uint32_t *path, uint32_t path_cap, uint32_t *status, uint32_t *pops, uint32_t *total);
+/* Measurement probe (not part of the reference interface): the last space-time A* call of the context, summed
+ * over its batches, HIP-event timed on the context stream (0 with timing off). out[0] = ms of the reservation
+ * set's build and upload, out[1] = ms of the search kernel, out[2] = ms of the path packing, out[3] = batches,
+ * out[4] = search waves resident per batch. */
+int tsw_probe_st_astar(const tsw_ctx *ctx, double *out);
 
 /* K1: BFS distance tables for k goal cells, u16 per cell, row-major
  * (TSW_DIST_INF for blocked/unreachable). out: host buffer k*w*h. */

@@ -46,6 +46,8 @@ AUDIT_KINDS = ("colocation", "swap", "jump", "off_map", "bad_state")
 # tsw_task_timeline (include/tswap.h): dispatch rules, words per task
 TSW_TL_NEAREST, TSW_TL_STREAM, TSW_TL_NTASK = 0, 1, 4
 TIMELINE_RULES = {"nearest": TSW_TL_NEAREST, "stream": TSW_TL_STREAM}
+# tsw_astar_reserved (include/tswap.h): per-query status
+TSW_SP_FOUND, TSW_SP_NONE, TSW_SP_CAPACITY = 0, 1, 2
 DIST_INF = 0xFFFF
 
 
@@ -163,6 +165,7 @@ EXPORTED_SYMBOLS = (
     "tsw_host_next_hop_codes", "tsw_nearby", "tsw_decide_fleet", "tsw_fleet_apply", "tsw_fleet_run",
     "tsw_fleet_mapd", "tsw_audit_records", "tsw_audit_records_device", "tsw_plan_mapd_online",
     "tsw_task_timeline", "tsw_task_timeline_device", "tsw_probe_timeline",
+    "tsw_astar_reserved", "tsw_host_astar_reserved", "tsw_probe_st_astar",
 )
 
 # tsw_resolve_fn (include/tswap.h): int (*)(void *user, uint32_t k, const uint32_t *start,
@@ -229,6 +232,13 @@ def load_library(path: str = LIB_PATH):
     lib.tsw_task_timeline_device.restype = ctypes.c_int
     lib.tsw_probe_timeline.argtypes = [vp, P(ctypes.c_double)]
     lib.tsw_probe_timeline.restype = ctypes.c_int
+    st_args = [P(u32), P(u32), P(u32), u32, P(u32), u32, P(u32), u32, u32, u32, P(u32), P(u32), u32, P(u32), P(u32), P(u32)]
+    lib.tsw_astar_reserved.argtypes = [vp, *st_args]
+    lib.tsw_astar_reserved.restype = ctypes.c_int
+    lib.tsw_host_astar_reserved.argtypes = [P(ctypes.c_uint8), u32, u32, *st_args]
+    lib.tsw_host_astar_reserved.restype = ctypes.c_int
+    lib.tsw_probe_st_astar.argtypes = [vp, P(ctypes.c_double)]
+    lib.tsw_probe_st_astar.restype = ctypes.c_int
     lib.tsw_dist_tables.argtypes = [vp, P(u32), u32, P(ctypes.c_uint16)]
     lib.tsw_dist_tables_device.argtypes = [vp, P(u32), u32, vp]
     lib.tsw_import_tables_device.argtypes = [vp, P(u32), u32, vp]
@@ -299,6 +309,52 @@ def host_next_hop_codes(grid, start, goal) -> np.ndarray:
     if rc != TSW_OK:
         raise TswapError(rc, "tsw_host_next_hop_codes: bad grid, or a start / goal that is not a free cell")
     return out
+
+
+def _st_astar_call(call, what, start, goal, start_time, node_res, edge_res, max_time, max_nodes):
+    """The argument handling tsw_astar_reserved and tsw_host_astar_reserved share: call(*args) -> rc. A size
+    query first, then the call with a path array of that size — the searches run TWICE; when the paths' upper
+    bound (every query arriving at max_time, sum of max_time + 1 - start_time) is at most 2^24 entries the bound is
+    the first call's capacity and one call does."""
+    st = np.ascontiguousarray(start, dtype=np.uint32).reshape(-1)
+    gl = np.ascontiguousarray(goal, dtype=np.uint32).reshape(-1)
+    t0 = np.ascontiguousarray(start_time, dtype=np.uint32).reshape(-1)
+    if t0.size == 1 and st.size != 1:
+        t0 = np.full(st.size, t0[0], dtype=np.uint32)
+    if not (st.size == gl.size == t0.size):
+        raise TswapError(TSW_EINVAL, "start, goal and start_time must have the same length")
+    nr = np.zeros((0, 2), np.uint32) if node_res is None else np.ascontiguousarray(node_res, dtype=np.uint32).reshape(-1, 2)
+    er = np.zeros((0, 3), np.uint32) if edge_res is None else np.ascontiguousarray(edge_res, dtype=np.uint32).reshape(-1, 3)
+    k = st.size
+    off = np.zeros(k + 1, dtype=np.uint32)
+    status = np.zeros(k, dtype=np.uint32)
+    pops = np.zeros(k, dtype=np.uint32)
+    total = ctypes.c_uint32(0)
+    bound = int(np.maximum(np.int64(max_time) + 1 - t0.astype(np.int64), 0).sum())
+    cap = bound if bound <= (1 << 24) else 0
+    for _ in range(2):
+        path = np.zeros(cap, dtype=np.uint32)
+        rc = call(_u32p(st), _u32p(gl), _u32p(t0), k, _u32p(nr) if nr.size else None, nr.shape[0],
+                  _u32p(er) if er.size else None, er.shape[0], int(max_time), int(max_nodes), _u32p(off),
+                  _u32p(path) if cap else None, cap, _u32p(status), _u32p(pops), ctypes.byref(total))
+        if rc != TSW_EOVERFLOW or total.value <= cap:
+            break
+        cap = total.value
+    if rc != TSW_OK:
+        raise TswapError(rc, what())
+    return off, path[:total.value].copy(), status, pops
+
+
+def host_astar_reserved(grid, start, goal, start_time, node_res=None, edge_res=None, max_time: int = 1 << 20,
+                        max_nodes: int = 65536):
+    """tsw_host_astar_reserved: astar_with_reservation (a_star.rs:32-112) for k queries on the calling thread
+    — no context, no device. Arguments and results as Planner.astar_reserved."""
+    lib = load_library(LIB_PATH)
+    cells, w, h = grid_to_bytes(grid)
+    cp = cells.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+    return _st_astar_call(lambda *a: lib.tsw_host_astar_reserved(cp, w, h, *a),
+                          lambda: "tsw_host_astar_reserved: bad grid, cell, time or cap",
+                          start, goal, start_time, node_res, edge_res, max_time, max_nodes)
 
 
 class Planner:
@@ -698,6 +754,30 @@ class Planner:
         self._check(self._lib.tsw_probe_timeline(self._ctx, out))
         return {"events_ms": out[0], "replay_ms": out[1], "attach_ms": out[2], "takes": int(out[3]),
                 "candidates_scanned": int(out[4])}
+
+    # --- space-time A* with reservations -------------------------------------
+    def astar_reserved(self, start, goal, start_time, node_res=None, edge_res=None, max_time: int = 1 << 20,
+                       max_nodes: int = 65536):
+        """tsw_astar_reserved: astar_with_reservation (a_star.rs:32-112) for k queries on the device. start,
+        goal: (k,) free cell ids; start_time: (k,) or one time for all; node_res: (n, 2) uint32 rows (cell, t);
+        edge_res: (n, 3) uint32 rows (from, to, t); max_time: a popped node with f > max_time ends a search;
+        max_nodes: pushes a search may make. Returns (path_off (k + 1,), path, status (k,) of TSW_SP_*, pops (k,)):
+        query i's path is path[path_off[i]:path_off[i + 1]], the cell at time start_time[i] + j at index j, empty
+        unless status[i] == TSW_SP_FOUND. Cost: when sum(max_time + 1 - start_time) over the queries exceeds 2^24 (large
+        k with a generous max_time, the default 2^20 among them) the wrapper asks for the paths' size first and the
+        searches run twice; give the tightest max_time you can. The context keeps the call's scratch (see
+        include/tswap.h: 1.5 MiB per search wave in flight at the default max_nodes, 12 GiB for 8,192 queries or
+        more) until it is closed; a smaller max_nodes shrinks it."""
+        return _st_astar_call(lambda *a: self._lib.tsw_astar_reserved(self._ctx, *a),
+                              lambda: self._lib.tsw_last_error(self._ctx).decode(),
+                              start, goal, start_time, node_res, edge_res, max_time, max_nodes)
+
+    def st_astar_probe(self) -> dict:
+        """tsw_probe_st_astar: the last astar_reserved call's kernel times (ms), batches and resident waves."""
+        out = (ctypes.c_double * 5)()
+        self._check(self._lib.tsw_probe_st_astar(self._ctx, out))
+        return {"reservations_ms": out[0], "search_ms": out[1], "pack_ms": out[2], "batches": int(out[3]),
+                "waves": int(out[4])}
 
     # --- get_path -----------------------------------------------------------
     def get_path_next(self, start: np.ndarray, goal: np.ndarray):

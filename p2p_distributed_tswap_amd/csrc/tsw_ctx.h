@@ -1,9 +1,10 @@
-// tsw_ctx.h — the host runtime's context (struct tsw_ctx behind include/tswap.h) and what its seven
+// tsw_ctx.h — the host runtime's context (struct tsw_ctx behind include/tswap.h) and what its
 // translation units share: tsw_ctx.hip (create / destroy, tunables, stats), tsw_tables.hip (K1 and the
 // goal-table store), tsw_query.hip (K3 scratch, queue and passes), tsw_plan_host.hip (the plan runner and
 // its host A* service), tsw_online_host.hip (the plan with release times, run in segments),
-// tsw_fleet_host.hip (decide and the fleet entry points) and tsw_audit_host.hip (the
-// audit of plan records). Host code only; every
+// tsw_fleet_host.hip (decide and the fleet entry points), tsw_audit_host.hip (the
+// audit of plan records), tsw_timeline_host.hip (the task timeline) and tsw_st_astar_host.hip (the space-time
+// A* with reservations). Host code only; every
 // device buffer of the context is a DevBuf / PinnedBuf member (tsw_buf.h) and is freed with it.
 // Nothing here depends on the build flavour: only tsw_ctx.hip is compiled per flavour.
 #pragma once
@@ -109,6 +110,12 @@ struct Tunables {
   uint32_t host_delay_us = 0;     // TSW_HOST_ASTAR_DELAY_US (test knob): the host holds every reply back this long
   uint32_t host_ring = 0;         // TSW_HOST_ASTAR_RING (test knob): request / reply ring entries (0: HOST_RING_ENTRIES)
   uint32_t host_early = 1;        // TSW_HOST_ASTAR_EARLY: urgent pairs asked of the host when queued (0: off; 2: and coop_wait leaves the host alone)
+
+  // space-time A* (tsw_st_astar_host.hip), test knobs: they force the paths a small case never takes
+  uint32_t st_heap = 0;           // TSW_ST_HEAP: LDS heap entries per wave (0: st_astar_config's; a small one spills to the global heap early)
+  uint32_t st_waves = 0;          // TSW_ST_WAVES: waves of a launch at most (0: what the device seats; a small one gives a wave several queries)
+  uint32_t st_seg_words = 0;      // TSW_ST_SEG_WORDS: path-segment words of one batch at most (0: by the free memory; a small one cuts a call into batches)
+  uint32_t st_tag0 = 1;           // TSW_ST_TAG0: the context's first visited-table tag (near 2^18 - 1: the tags wrap and the tables are wiped)
 
   static Tunables from_env();  // tsw_ctx.hip: the only reader of the environment
 };
@@ -278,6 +285,16 @@ struct tsw_ctx {
   DevBuf<uint8_t> d_tl_ev;
   DevBuf<uint32_t> d_tl_w;
   double tl_last[5] = {};
+  // tsw_astar_reserved scratch (grow-only, tsw_st_astar_host.hip): the reservation set, the running waves'
+  // visited tables and overflow heaps, one block of words per batch (queries up, results down), the batch's
+  // path segments with their offsets, and the packed paths. st_vis_words / st_vis_wiped / st_tag: the table
+  // geometry the tags in d_st_vis belong to, how many tables of it have been wiped, and the next unused tag.
+  // st_last: what tsw_probe_st_astar reports of the last call.
+  DevBuf<uint64_t> d_st_res, d_st_vis, d_st_heap, d_st_segoff;
+  DevBuf<uint32_t> d_st_w, d_st_seg, d_st_path;
+  uint64_t st_vis_words = 0;
+  uint32_t st_vis_wiped = 0, st_tag = 1;
+  double st_last[5] = {};
 
   // stats / timing
   tsw_stats st{};

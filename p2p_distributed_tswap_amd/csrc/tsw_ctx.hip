@@ -92,6 +92,10 @@ Tunables Tunables::from_env() {
   t.host_delay_us = (uint32_t)num("TSW_HOST_ASTAR_DELAY_US", 0, 1000000, 0);
   t.host_ring = (uint32_t)num("TSW_HOST_ASTAR_RING", 8, 1 << 14, 0);
   t.host_early = (uint32_t)num("TSW_HOST_ASTAR_EARLY", 0, 2, t.host_early);
+  t.st_heap = (uint32_t)num("TSW_ST_HEAP", 0, 512, 0);
+  t.st_waves = (uint32_t)num("TSW_ST_WAVES", 0, 1 << 20, 0);
+  t.st_seg_words = (uint32_t)num("TSW_ST_SEG_WORDS", 0, 1 << 28, 0);
+  t.st_tag0 = (uint32_t)num("TSW_ST_TAG0", 1, (1 << 18) - 1, 1);
 #endif
   return t;
 }

@@ -8,6 +8,7 @@
 //   workers   worker_config, worker_layout, the k_astar_wave sizes  (tsw_worker.h, tsw_astar.hip)
 //   K1        the five kernels' carve sizes and fit tests, choose_bfs (tsw_bfs*.hip, run_bfs)
 //   K8        the task timeline's tiles, workgroups and LDS share     (tsw_timeline.hip)
+//   K9        the space-time A*'s waves, LDS heap and staged bitmap  (tsw_st_astar.hip)
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -437,5 +438,35 @@ inline uint32_t tl_lds_candidates(uint32_t m, int max_lds) {
   return (uint32_t)(std::min(fit, want) * TL_B_BLOCK);
 }
 inline uint32_t tl_attach_workgroups(uint32_t m) { return std::max<uint32_t>(tl_tiles(m, TL_C_BLOCK), 1u); }
+
+// ---- K9: the space-time A* with reservations (tsw_st_astar.hip) -------------------------------------
+// One wave per query, ST_WPB waves per workgroup. A wave's pop is a chain of dependent global loads (the
+// reservation set and its visited table), so the rule is "as many waves per CU as the hardware seats" (32, or
+// what the workgroups' LDS leaves: 20 with a staged bitmap near its 16 KiB limit):
+// the LDS heap is 512 entries a wave — searches with reservations peak at a few hundred, a larger heap moves
+// to the wave's global overflow heap — and the free-cell bitmap is staged once per workgroup while it is
+// small. Carve: ST_WPB heaps, then the bitmap.
+constexpr uint32_t ST_WPB = 4u, ST_HEAP_LDS = 512u, ST_HEAP_LDS_MIN = 64u, ST_FB_LDS_MAX = 16u * 1024u;
+constexpr uint32_t ST_WAVES_PER_CU = 32u;
+struct StAstarCfg {
+  uint32_t wpb, hl, fb_lds;  // waves per workgroup, LDS heap entries per wave, bitmap staged in LDS
+  uint32_t waves;            // waves the device seats at once
+  size_t lds;                // dynamic LDS of one workgroup
+};
+// hl_want: Tunables::st_heap (0: ST_HEAP_LDS)
+inline StAstarCfg st_astar_config(const DevGrid& G, int max_lds, int num_cu, uint32_t hl_want = 0u) {
+  const size_t room = (size_t)std::max(max_lds, 0);
+  const size_t fbb = ((size_t)G.H * G.Ww * 4u + 15u) / 16u * 16u;
+  StAstarCfg c{};
+  c.wpb = ST_WPB;
+  c.hl = hl_want ? std::min(std::max(hl_want, 4u), ST_HEAP_LDS) : ST_HEAP_LDS;
+  while (c.hl > ST_HEAP_LDS_MIN && (size_t)c.wpb * c.hl * 8u > room) c.hl >>= 1;
+  const size_t heaps = (size_t)c.wpb * c.hl * 8u;
+  c.fb_lds = fbb <= ST_FB_LDS_MAX && heaps + fbb <= room ? 1u : 0u;
+  c.lds = heaps + (c.fb_lds ? fbb : 0u);
+  const uint32_t wg_per_cu = (uint32_t)std::min<size_t>(ST_WAVES_PER_CU / c.wpb, std::max<size_t>(1u, CU_LDS_BYTES / c.lds));
+  c.waves = (uint32_t)std::max(num_cu, 1) * wg_per_cu * c.wpb;
+  return c;
+}
 
 }  // namespace tsw

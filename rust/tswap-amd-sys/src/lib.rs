@@ -65,6 +65,29 @@ pub const TSW_TL_NEAREST: u32 = 0;
 pub const TSW_TL_STREAM: u32 = 1;
 pub const TSW_TL_NTASK: u32 = 4;
 
+/// `tsw_astar_reserved`'s per-query status: a path, none (horizon reached or the heap ran empty), or the
+/// query's `max_nodes` pushes used up.
+pub const TSW_SP_FOUND: u32 = 0;
+pub const TSW_SP_NONE: u32 = 1;
+pub const TSW_SP_CAPACITY: u32 = 2;
+
+/// `tsw_node_res`: a reserved vertex `(Point, time)` of `NodeReservation` (a_star.rs:6), the point as a cell id.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq, Hash)]
+pub struct TswNodeRes {
+    pub cell: u32,
+    pub t: u32,
+}
+
+/// `tsw_edge_res`: a reserved edge `((Point, Point), time)` of `EdgeReservation` (a_star.rs:7).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq, Hash)]
+pub struct TswEdgeRes {
+    pub from: u32,
+    pub to: u32,
+    pub t: u32,
+}
+
 /// `tsw_resolve_fn`: the caller's K3 for `tsw_plan_mapd_resolved` — fill `code[i]` (0..3 S,E,N,W,
 /// 4 stay) for get_path(start[i], goal[i]) and return 0 (e.g. send each pair to its goal's owner).
 pub type TswResolveFn =
@@ -238,6 +261,19 @@ extern "C" {
                                     starts: *const TswPoint, tasks: *const TswTask, release: *const u32, m: u32,
                                     rule: u32, sum: *mut TswTimeline, task: *mut u32) -> c_int;
     pub fn tsw_probe_timeline(ctx: *const TswCtx, out: *mut f64) -> c_int;
+    /// `astar_with_reservation` (a_star.rs:32-112) for k queries on the device; paths in CSR form
+    /// (`path_off`: k + 1 entries), `path` null with `path_cap` 0 is a size query (TSW_EOVERFLOW, `total` valid).
+    pub fn tsw_astar_reserved(ctx: *mut TswCtx, start: *const u32, goal: *const u32, start_time: *const u32, k: u32,
+                              node_res: *const TswNodeRes, n_node: u32, edge_res: *const TswEdgeRes, n_edge: u32,
+                              max_time: u32, max_nodes: u32, path_off: *mut u32, path: *mut u32, path_cap: u32,
+                              status: *mut u32, pops: *mut u32, total: *mut u32) -> c_int;
+    /// The same search on the calling thread: no context, no device.
+    pub fn tsw_host_astar_reserved(cells: *const u8, w: u32, h: u32, start: *const u32, goal: *const u32,
+                                   start_time: *const u32, k: u32, node_res: *const TswNodeRes, n_node: u32,
+                                   edge_res: *const TswEdgeRes, n_edge: u32, max_time: u32, max_nodes: u32,
+                                   path_off: *mut u32, path: *mut u32, path_cap: u32, status: *mut u32,
+                                   pops: *mut u32, total: *mut u32) -> c_int;
+    pub fn tsw_probe_st_astar(ctx: *const TswCtx, out: *mut f64) -> c_int;
     pub fn tsw_dist_tables(ctx: *mut TswCtx, goals: *const u32, k: u32, out: *mut u16) -> c_int;
     pub fn tsw_dist_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_out: *mut u16) -> c_int;
     pub fn tsw_import_tables_device(ctx: *mut TswCtx, goals: *const u32, k: u32, dev_tables: *const u16) -> c_int;
