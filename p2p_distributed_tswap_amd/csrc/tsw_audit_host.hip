@@ -3,18 +3,20 @@
 // and nothing else of it: the table store, the queues and the stats stay as they were. Host code only.
 #include "tsw_audit.h"
 #include "tsw_ctx.h"
+#include "tsw_layout.h"
 
-// scratch that does not fit is TSW_ENOMEM here, not TSW_EHIP (grow_synced's code)
-template <class T>
-static int audit_grow(tsw_ctx* c, DevBuf<T>& b, size_t need, const char* what) {
-  if (b.holds(need)) return TSW_OK;
-  HIPCHK(hipStreamSynchronize(c->s));
-  if (hipError_t e = b.grow(need); e != hipSuccess) {
-    (void)hipGetLastError();  // the failed allocation is reported by the code, not left pending
-    RET(e == hipErrorOutOfMemory ? TSW_ENOMEM : TSW_EHIP, std::string("audit scratch (") + what + "): " + hipGetErrorString(e));
-  }
+namespace tsw {
+
+int upload_records(tsw_ctx* c, const tsw_rec* rec, uint32_t n, uint32_t T, uint32_t stride, const char* label) {
+  TRY(scratch_grow(c, c->d_aud_rec, (size_t)n * T, label, "records"));
+  if (stride == T)
+    HIPCHK(hipMemcpyAsync(c->d_aud_rec, rec, (size_t)n * T * 8, hipMemcpyHostToDevice, c->s));
+  else
+    HIPCHK(hipMemcpy2DAsync(c->d_aud_rec, (size_t)T * 8, rec, (size_t)stride * 8, (size_t)T * 8, n, hipMemcpyHostToDevice, c->s));
   return TSW_OK;
 }
+
+}  // namespace tsw
 
 extern "C" {
 
@@ -38,31 +40,31 @@ static int audit_device(tsw_ctx* c, const unsigned long long* d_rec, uint32_t n,
   A.rec = d_rec;
   A.freebits = c->G.freebits;
   A.G = aud_workgroups(T, ncell, in_lds);
-  // the outputs in one block: first (AUD_NKIND 64-bit words) | col (T * AUD_NCOL) | agent (n * AUD_NAGENT)
-  const size_t col_words = (size_t)T * AUD_NCOL, agent_words = agent ? (size_t)n * AUD_NAGENT : 0;
-  TRY(audit_grow(c, c->d_aud_out, 2 * AUD_NKIND + col_words + agent_words, "counters"));
-  TRY(audit_grow(c, c->d_aud_cid, (size_t)T * n, "transpose"));
-  if (!in_lds) TRY(audit_grow(c, c->d_aud_tab, (size_t)A.G * ncell, "occupancy tables"));
-  A.first = reinterpret_cast<unsigned long long*>(c->d_aud_out.p);  // the allocation is 8-byte aligned
-  A.col = c->d_aud_out + 2 * AUD_NKIND;
-  A.agent = agent ? A.col + col_words : nullptr;
+  const AuditOutLayout L = audit_out_layout(n, T, agent != nullptr, AUD_NKIND, AUD_NCOL, AUD_NAGENT);
+  TRY(scratch_grow(c, c->d_aud_out, L.total, "audit", "counters"));
+  TRY(scratch_grow(c, c->d_aud_cid, (size_t)T * n, "audit", "transpose"));
+  if (!in_lds) TRY(scratch_grow(c, c->d_aud_tab, (size_t)A.G * ncell, "audit", "occupancy tables"));
+  uint32_t* const d = c->d_aud_out.p;
+  A.first = reinterpret_cast<unsigned long long*>(d + L.first);
+  A.col = d + L.col;
+  A.agent = agent ? d + L.agent : nullptr;
   A.cid = c->d_aud_cid;
   A.tab = in_lds ? nullptr : c->d_aud_tab.p;
   HIPCHK(hipMemsetAsync(A.first, 0xFF, AUD_NKIND * 8, c->s));
-  HIPCHK(hipMemsetAsync(A.col, 0, col_words * 4, c->s));
+  HIPCHK(hipMemsetAsync(A.col, 0, L.col_words * 4, c->s));
   if (agent) {  // moves, deliveries, columns = 0; first = 0xFFFFFFFF
-    HIPCHK(hipMemsetAsync(A.agent, 0, agent_words * 4, c->s));
+    HIPCHK(hipMemsetAsync(A.agent, 0, L.agent_words * 4, c->s));
     HIPCHK(hipMemset2DAsync(A.agent + 3, AUD_NAGENT * 4, 0xFF, 4, n, c->s));
   }
   if (!in_lds) HIPCHK(hipMemsetAsync(A.tab, 0, (size_t)A.G * ncell * 8, c->s));
   HIPCHK(launch_audit_rows(A, c->s));
   HIPCHK(launch_audit_columns(A, c->max_lds, c->s));
   // first | col come down together; the sums are the host's (T * AUD_NCOL additions)
-  std::vector<uint32_t> h(2 * AUD_NKIND + col_words);
-  HIPCHK(hipMemcpyAsync(h.data(), c->d_aud_out, h.size() * 4, hipMemcpyDeviceToHost, c->s));
-  if (agent) HIPCHK(hipMemcpyAsync(agent, A.agent, agent_words * 4, hipMemcpyDeviceToHost, c->s));
+  std::vector<uint32_t> h(L.col + L.col_words);
+  HIPCHK(hipMemcpyAsync(h.data(), d + L.first, h.size() * 4, hipMemcpyDeviceToHost, c->s));
+  if (agent) HIPCHK(hipMemcpyAsync(agent, A.agent, L.agent_words * 4, hipMemcpyDeviceToHost, c->s));
   HIPCHK(hipStreamSynchronize(c->s));
-  const uint32_t* hc = h.data() + 2 * AUD_NKIND;
+  const uint32_t* hc = h.data() + L.col;
   audit_empty(sum);
   for (uint32_t t = 0; t < T; ++t) {
     const uint32_t* w = hc + (size_t)t * AUD_NCOL;
@@ -78,13 +80,13 @@ static int audit_device(tsw_ctx* c, const unsigned long long* d_rec, uint32_t n,
   }
   for (uint32_t k = 0; k < AUD_NKIND; ++k) {
     unsigned long long key;
-    std::memcpy(&key, h.data() + 2 * k, 8);
+    std::memcpy(&key, h.data() + L.first + 2 * k, 8);
     if (key != ~0ull) {
       sum->first_t[k] = (uint32_t)(key >> 32);
       sum->first_agent[k] = (uint32_t)key;
     }
   }
-  if (col) std::memcpy(col, hc, col_words * 4);
+  if (col) std::memcpy(col, hc, L.col_words * 4);
   return TSW_OK;
 }
 
@@ -120,11 +122,7 @@ int tsw_audit_records(tsw_ctx* c, const tsw_rec* rec, uint32_t n, uint32_t T, ui
   if (empty) return TSW_OK;
   TRY(set_device(c));
   // columns 0 .. T - 1 of every row go up, packed: the device copy has T records per row
-  TRY(audit_grow(c, c->d_aud_rec, (size_t)n * T, "records"));
-  if (stride == T)
-    HIPCHK(hipMemcpyAsync(c->d_aud_rec, rec, (size_t)n * T * 8, hipMemcpyHostToDevice, c->s));
-  else
-    HIPCHK(hipMemcpy2DAsync(c->d_aud_rec, (size_t)T * 8, rec, (size_t)stride * 8, (size_t)T * 8, n, hipMemcpyHostToDevice, c->s));
+  TRY(upload_records(c, rec, n, T, stride, "audit"));
   return audit_device(c, c->d_aud_rec, n, T, T, sum, col, agent);
 }
 

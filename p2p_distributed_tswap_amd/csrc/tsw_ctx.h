@@ -269,7 +269,7 @@ struct tsw_ctx {
   DevBuf<uint32_t> d_grec;
   // temporaries
   DevBuf<uint32_t> d_tmp_a, d_tmp_b, d_tmp_c;
-  // tsw_nearby / tsw_decide_fleet scratch (grow-only): [0] bins, counts and offsets (sized by the fleet
+  // tsw_nearby / tsw_decide_fleet scratch (grow-only, laid out by tsw_layout.h): [0] bins, counts and offsets (sized by the fleet
   // and the grid), [1] the lists and k_decide's arrays (sized by the lists' total)
   // [2] tsw_fleet_run's records (v_rec | g_rec) or tsw_fleet_mapd's (out | goal_out | task_out)
   DevBuf<uint32_t> d_fleet[3];
@@ -280,8 +280,8 @@ struct tsw_ctx {
   DevBuf<uint32_t> d_aud_cid, d_aud_out;
   DevBuf<unsigned long long> d_aud_tab;
   // tsw_task_timeline scratch (grow-only): pass A's event table (T * n bytes) and every word array of a
-  // call in one block (timeline_device, tsw_timeline_host.hip, lays it out); records that come from the host
-  // go up into d_aud_rec, the audit's. tl_last: what tsw_probe_timeline reports of the last call.
+  // call in one block (timeline_layout, tsw_layout.h); records that come from the host go up into d_aud_rec,
+  // the audit's (upload_records). tl_last: what tsw_probe_timeline reports of the last call.
   DevBuf<uint8_t> d_tl_ev;
   DevBuf<uint32_t> d_tl_w;
   double tl_last[5] = {};
@@ -419,6 +419,23 @@ int grow_synced(tsw_ctx* c, DevBuf<T>& b, size_t need) {
   return TSW_OK;
 }
 
+// The same for the scratch of the audit, the timeline and the space-time A*: a block that does not fit is
+// TSW_ENOMEM, not TSW_EHIP, and the message reads "<label> scratch (<what>): <the HIP error>".
+template <class T>
+int scratch_grow(tsw_ctx* c, DevBuf<T>& b, size_t need, const char* label, const char* what) {
+  if (b.holds(need)) return TSW_OK;
+  HIPCHK(hipStreamSynchronize(c->s));
+  if (hipError_t e = b.grow(need); e != hipSuccess) {
+    (void)hipGetLastError();  // the failed allocation is reported by the code, not left pending
+    RET(e == hipErrorOutOfMemory ? TSW_ENOMEM : TSW_EHIP, std::string(label) + " scratch (" + what + "): " + hipGetErrorString(e));
+  }
+  return TSW_OK;
+}
+
+// tsw_audit_host.hip: columns 0 .. T - 1 of every row of the caller's records (n rows of `stride`) packed into
+// d_aud_rec, T records per row, on the stream; label: scratch_grow's
+int upload_records(tsw_ctx* c, const tsw_rec* rec, uint32_t n, uint32_t T, uint32_t stride, const char* label);
+
 // The pickup point the nearest-pickup choice measures to, x | y << 16: the raw point with its coordinates
 // clamped to 0xFFFE (plan_validate_index says why that cannot change the winner). tsw_task_timeline replays
 // the choice from the same word.
@@ -449,6 +466,33 @@ struct Timer {
       hipEventRecord(b, c->s);
       c->pending.push_back({cat, a, b});
     }
+  }
+};
+
+// The passes of one call timed apart, for the tsw_probe_* of a call: N events from the pool while the context
+// times (none otherwise), mark(k) on the stream between the passes, elapsed(k) from mark k to mark k + 1 once the
+// stream is drained (0 without timing). The events go back to the pool on every way out of the call.
+template <int N>
+struct PassTimer {
+  tsw_ctx* c;
+  hipEvent_t ev[N] = {};
+  explicit PassTimer(tsw_ctx* c_) : c(c_) {
+    if (c->timing)
+      for (hipEvent_t& e : ev) e = ev_get(c);
+  }
+  PassTimer(const PassTimer&) = delete;
+  PassTimer& operator=(const PassTimer&) = delete;
+  ~PassTimer() {
+    for (hipEvent_t e : ev)
+      if (e) c->pool.push_back(e);
+  }
+  void mark(int k) {
+    if (ev[k]) hipEventRecord(ev[k], c->s);
+  }
+  double elapsed(int k) const {
+    float ms = 0.f;
+    if (ev[k] && ev[k + 1] && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f;
+    return ms;
   }
 };
 

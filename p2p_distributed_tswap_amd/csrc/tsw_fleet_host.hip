@@ -4,6 +4,7 @@
 #include "tsw_ctx.h"
 #include "tsw_fleet.h"
 #include "tsw_fleet_mapd.h"
+#include "tsw_layout.h"
 #include "tsw_nearby.h"
 
 extern "C" {
@@ -43,25 +44,26 @@ static int decide_impl(tsw_ctx* c, const uint32_t* my_v, const uint32_t* my_g, u
     if (cell_id_ok(c, nb_g[k]) && cell_id_ok(c, nb_v[k])) goals.push_back(nb_g[k]);
   TRY(ensure_tables(c, goals, true));
   // device copies: inputs, outputs, pending lists (ping-pong)
-  const size_t nb = std::max<uint32_t>(tot, 1u);
+  const DecideLayout L = decide_layout(n, tot);
   DevBuf<uint32_t> buf;
-  HIPCHK(buf.alloc(2 * (size_t)n + (n + 1) + 2 * nb + 4 * (size_t)n + (tot + n) + 2 * (size_t)n + 2));
+  HIPCHK(buf.alloc(L.total));
+  uint32_t* const d = buf.p;
   DecideDev D{};
   D.n = n;
   D.tot = tot;
-  D.v = buf.p;
-  D.g = D.v + n;
-  D.off = D.g + n;
-  D.nv = D.off + n + 1;
-  D.ng = D.nv + nb;
-  D.act = D.ng + nb;
-  D.cell = D.act + n;
-  D.par = D.cell + n;
-  D.np = D.par + n;
-  D.part = D.np + n;
-  D.q0 = D.part + tot + n;
-  D.q1 = D.q0 + n;
-  D.cnt = D.q1 + n;
+  D.v = d + L.v;
+  D.g = d + L.g;
+  D.off = d + L.off;
+  D.nv = d + L.nv;
+  D.ng = d + L.ng;
+  D.act = d + L.act;
+  D.cell = d + L.cell;
+  D.par = d + L.par;
+  D.np = d + L.np;
+  D.part = d + L.part;
+  D.q0 = d + L.q0;
+  D.q1 = d + L.q1;
+  D.cnt = d + L.cnt;
   HIPCHK(hipMemcpyAsync(D.v, my_v, n * 4ull, hipMemcpyHostToDevice, c->s));
   HIPCHK(hipMemcpyAsync(D.g, my_g, n * 4ull, hipMemcpyHostToDevice, c->s));
   HIPCHK(hipMemcpyAsync(D.off, nb_off, (n + 1) * 4ull, hipMemcpyHostToDevice, c->s));
@@ -158,6 +160,7 @@ static int fleet_hgrow(tsw_ctx* c, size_t words) {
 struct FleetLists {
   NearbyArgs A{};
   uint32_t *v = nullptr, *g = nullptr;  // device copies (g only when given)
+  uint32_t* pad = nullptr;              // the spare word of the head's read-back (fleet_lists_count)
   uint32_t total = 0, maxlen = 0;
 };
 // The buffers of the count pass in d_fleet[0] (sized by the fleet and the grid), with `extra` more words
@@ -165,21 +168,22 @@ struct FleetLists {
 static int fleet_lists_setup(tsw_ctx* c, uint32_t n, uint32_t radius, FleetLists* S, size_t extra = 0,
                              uint32_t** extra_out = nullptr) {
   const uint32_t ncell = c->G.ncell;
-  const size_t nbs = std::max(nb_scan_blocks(ncell), nb_scan_blocks(n));
-  TRY(grow_synced(c, c->d_fleet[0], 4 + 2 * (size_t)n + ((size_t)ncell + 1) + 2 * (size_t)n + ((size_t)n + 1) + nbs + extra));
+  const FleetListsLayout L = fleet_lists_layout(n, ncell, std::max(nb_scan_blocks(ncell), nb_scan_blocks(n)), extra);
+  TRY(grow_synced(c, c->d_fleet[0], L.total));
   TRY(fleet_hgrow(c, 4 * (size_t)n + 4));
   uint32_t* d = c->d_fleet[0];
   NearbyArgs& A = S->A;
-  A.total64 = reinterpret_cast<unsigned long long*>(d);  // words 0-1 (the allocation is 8-byte aligned)
-  A.maxlen = d + 2;
-  A.cell_start = d + 4;  // right behind them: launch_nearby_count clears all three with one memset
-  S->v = A.cell_start + ncell + 1;
-  S->g = S->v + n;
-  A.rank = S->g + n;
-  A.sorted = A.rank + n;
-  A.off = A.sorted + n;
-  A.bsum = A.off + n + 1;
-  if (extra_out) *extra_out = A.bsum + nbs;
+  A.total64 = reinterpret_cast<unsigned long long*>(d + L.total64);
+  A.maxlen = d + L.maxlen;
+  S->pad = d + L.pad;
+  A.cell_start = d + L.cell_start;
+  S->v = d + L.v;
+  S->g = d + L.g;
+  A.rank = d + L.rank;
+  A.sorted = d + L.sorted;
+  A.off = d + L.off;
+  A.bsum = d + L.bsum;
+  if (extra_out) *extra_out = d + L.extra;
   A.W = c->G.W;
   A.H = c->G.H;
   A.n = n;
@@ -192,10 +196,9 @@ static int fleet_lists_setup(tsw_ctx* c, uint32_t n, uint32_t radius, FleetLists
 // pad_src (device, may be nullptr) -> *pad: one more word for the host in the pad slot of the same 16-byte
 // read-back (tsw_fleet_run: the previous tick's "changed" word, so a tick adds no synchronise for it).
 static int fleet_lists_count(tsw_ctx* c, FleetLists* S, const uint32_t* pad_src = nullptr, uint32_t* pad = nullptr) {
-  uint32_t* d = c->d_fleet[0];
   HIPCHK(launch_nearby_count(S->A, c->s));
-  if (pad_src) HIPCHK(hipMemcpyAsync(d + 3, pad_src, 4, hipMemcpyDeviceToDevice, c->s));
-  HIPCHK(hipMemcpyAsync(c->h_fleet, d, 16, hipMemcpyDeviceToHost, c->s));  // total64, maxlen, pad
+  if (pad_src) HIPCHK(hipMemcpyAsync(S->pad, pad_src, 4, hipMemcpyDeviceToDevice, c->s));
+  HIPCHK(hipMemcpyAsync(c->h_fleet, S->A.total64, 16, hipMemcpyDeviceToHost, c->s));  // total64, maxlen, pad
   HIPCHK(hipStreamSynchronize(c->s));
   unsigned long long tot64 = 0;
   std::memcpy(&tot64, c->h_fleet, 8);
@@ -252,27 +255,28 @@ static int fleet_decide_device(tsw_ctx* c, const FleetLists& S, uint32_t part_ca
                                uint32_t** d_pout_out) {
   const uint32_t n = S.A.n;
   const uint32_t tot = S.total;
-  const size_t nb = std::max<uint32_t>(tot, 1u);
-  TRY(grow_synced(c, c->d_fleet[1], 3 * nb + 4 * (size_t)n + 2 * ((size_t)tot + n) + 2 * (size_t)n + 2 + ((size_t)n + 1)));
-  uint32_t* d_idx = c->d_fleet[1];
+  const FleetDecideLayout L = fleet_decide_layout(n, tot);
+  TRY(grow_synced(c, c->d_fleet[1], L.total));
+  uint32_t* const d = c->d_fleet[1];
+  uint32_t* d_idx = d + L.idx;
   DecideDev& D = *Dp;
   D.n = n;
   D.tot = tot;
   D.v = S.v;
   D.g = S.g;
   D.off = S.A.off;
-  D.nv = d_idx + nb;
-  D.ng = D.nv + nb;
-  D.act = D.ng + nb;  // act | cell | partner | part_off: one block, one copy back
-  D.cell = D.act + n;
-  D.par = D.cell + n;
-  uint32_t* d_poff = D.par + n;        // n + 1: participant offsets
-  D.np = d_poff + n + 1;
-  D.part = D.np + n;
-  D.q0 = D.part + tot + n;
-  D.q1 = D.q0 + n;
-  D.cnt = D.q1 + n;
-  uint32_t* d_pout = D.cnt + 2;        // tot + n: compacted participants (agent indices)
+  D.nv = d + L.nv;
+  D.ng = d + L.ng;
+  D.act = d + L.act;
+  D.cell = d + L.cell;
+  D.par = d + L.par;
+  uint32_t* d_poff = d + L.poff;  // n + 1: participant offsets
+  D.np = d + L.np;
+  D.part = d + L.part;
+  D.q0 = d + L.q0;
+  D.q1 = d + L.q1;
+  D.cnt = d + L.cnt;
+  uint32_t* d_pout = d + L.pout;  // tot + n: compacted participants (agent indices)
   // the lists, and in the same pass their cells and goals (nb_v / nb_g, what k_decide reads)
   HIPCHK(launch_nearby_fill(S.A, S.maxlen, d_idx, S.g, D.nv, D.ng, c->s));
   TRY(decide_rounds(c, D));
@@ -338,17 +342,15 @@ int tsw_decide_fleet(tsw_ctx* c, const uint32_t* v, const uint32_t* g, uint32_t 
 
 // ---- K5b: a tick's decisions applied (tsw_fleet.hip), and the lock-step run built on both ------------
 
-// words of the apply state behind n agents: g0, owner, opflag (n + 1), ops (2 n), the scan's block sums,
-// the changed word
-static size_t fleet_apply_words(uint32_t n) { return 5 * (size_t)n + 1 + nb_scan_blocks(n) + 1; }
-static void fleet_apply_layout(FleetApplyArgs* A, uint32_t* p, uint32_t n) {
+// the apply state of n agents at p (L: fleet_apply_layout(n, nb_scan_blocks(n)))
+static void fleet_apply_state(FleetApplyArgs* A, uint32_t* p, const FleetApplyLayout& L, uint32_t n) {
   A->n = n;
-  A->g0 = p;
-  A->owner = A->g0 + n;
-  A->opflag = A->owner + n;
-  A->ops = A->opflag + n + 1;
-  A->bsum = A->ops + 2 * (size_t)n;
-  A->changed = A->bsum + nb_scan_blocks(n);
+  A->g0 = p + L.g0;
+  A->owner = p + L.owner;
+  A->opflag = p + L.opflag;
+  A->ops = p + L.ops;
+  A->bsum = p + L.bsum;
+  A->changed = p + L.changed;
 }
 
 int tsw_fleet_apply(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n, const uint32_t* act, const uint32_t* cell,
@@ -386,39 +388,51 @@ int tsw_fleet_apply(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n, const uint
     }
   }
   TRY(set_device(c));
-  // one block up: v | g | act | cell | partner | part_off (n + 1, rebased to 0) | part
-  const size_t in_words = 6 * (size_t)n + 1 + ptot;
-  TRY(grow_synced(c, c->d_fleet[1], in_words + fleet_apply_words(n)));
-  TRY(fleet_hgrow(c, in_words));
+  // one block up, the same in the staging buffer and on the device (part_off rebased to 0); the apply state
+  // behind it on the device
+  const FleetApplyInLayout I = fleet_apply_in_layout(n, ptot);
+  const FleetApplyLayout L = fleet_apply_layout(n, nb_scan_blocks(n));
+  TRY(grow_synced(c, c->d_fleet[1], I.total + L.total));
+  TRY(fleet_hgrow(c, I.total));
   uint32_t* h = c->h_fleet;
-  std::memcpy(h, v, n * 4ull);
-  std::memcpy(h + n, g, n * 4ull);
-  std::memcpy(h + 2 * (size_t)n, act, n * 4ull);
-  std::memcpy(h + 3 * (size_t)n, cell, n * 4ull);
-  std::memcpy(h + 4 * (size_t)n, partner, n * 4ull);
-  for (uint32_t i = 0; i <= n; ++i) h[5 * (size_t)n + i] = part_off[i] - pbase;
-  if (ptot) std::memcpy(h + 6 * (size_t)n + 1, part + pbase, (size_t)ptot * 4);
+  std::memcpy(h + I.v, v, n * 4ull);
+  std::memcpy(h + I.g, g, n * 4ull);
+  std::memcpy(h + I.act, act, n * 4ull);
+  std::memcpy(h + I.cell, cell, n * 4ull);
+  std::memcpy(h + I.partner, partner, n * 4ull);
+  for (uint32_t i = 0; i <= n; ++i) h[I.part_off + i] = part_off[i] - pbase;
+  if (ptot) std::memcpy(h + I.part, part + pbase, (size_t)ptot * 4);
   uint32_t* d = c->d_fleet[1];
   FleetApplyArgs A{};
-  A.v = d;
-  A.g = d + n;
-  A.act = d + 2 * (size_t)n;
-  A.cell = d + 3 * (size_t)n;
-  A.partner = d + 4 * (size_t)n;
-  A.part_off = d + 5 * (size_t)n;
-  A.part = d + 6 * (size_t)n + 1;
-  fleet_apply_layout(&A, d + in_words, n);
+  A.v = d + I.v;
+  A.g = d + I.g;
+  A.act = d + I.act;
+  A.cell = d + I.cell;
+  A.partner = d + I.partner;
+  A.part_off = d + I.part_off;
+  A.part = d + I.part;
+  fleet_apply_state(&A, d + I.total, L, n);
   A.stamp = 1;
-  HIPCHK(hipMemcpyAsync(d, h, in_words * 4, hipMemcpyHostToDevice, c->s));
+  HIPCHK(hipMemcpyAsync(d, h, I.total * 4, hipMemcpyHostToDevice, c->s));
   HIPCHK(hipMemsetAsync(A.changed, 0, 4, c->s));
   HIPCHK(launch_fleet_apply(A, c->s));
-  // v | g, and the changed word behind them in the staging buffer
-  HIPCHK(hipMemcpyAsync(h, d, 2ull * n * 4, hipMemcpyDeviceToHost, c->s));
-  HIPCHK(hipMemcpyAsync(h + 2 * (size_t)n, A.changed, 4, hipMemcpyDeviceToHost, c->s));
+  // v | g, and the changed word in the staging buffer's next slot (act's: the inputs are on the device by now)
+  HIPCHK(hipMemcpyAsync(h + I.v, A.v, 2ull * n * 4, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipMemcpyAsync(h + I.act, A.changed, 4, hipMemcpyDeviceToHost, c->s));
   HIPCHK(hipStreamSynchronize(c->s));
-  if (h[2 * (size_t)n] == FLEET_STUCK) RET(TSW_EHIP, "internal: the goal-op rounds made no progress");
-  std::memcpy(v, h, n * 4ull);
-  std::memcpy(g, h + n, n * 4ull);
+  if (h[I.act] == FLEET_STUCK) RET(TSW_EHIP, "internal: the goal-op rounds made no progress");
+  std::memcpy(v, h + I.v, n * 4ull);
+  std::memcpy(g, h + I.g, n * 4ull);
+  return TSW_OK;
+}
+
+// The first `cols` of `stride` columns of each of n rows, elements of `elem` bytes, from the device's records to
+// the caller's of the same stride, on the stream; the later columns stay as the caller left them.
+static int download_columns(tsw_ctx* c, void* host, const void* dev, size_t n, size_t cols, size_t stride, size_t elem) {
+  if (cols == stride)
+    HIPCHK(hipMemcpyAsync(host, dev, n * stride * elem, hipMemcpyDeviceToHost, c->s));
+  else
+    HIPCHK(hipMemcpy2DAsync(host, stride * elem, dev, stride * elem, cols * elem, n, hipMemcpyDeviceToHost, c->s));
   return TSW_OK;
 }
 
@@ -437,14 +451,8 @@ static int fleet_run_finish(tsw_ctx* c, int rc, const FleetLists& S, FleetApplyA
     HIPCHK(hipMemcpyAsync(c->h_fleet, S.v, 2ull * n * 4, hipMemcpyDeviceToHost, c->s));
     uint32_t* host_rec[2] = {v_rec, g_rec};
     uint32_t* dev_rec[2] = {A.v_rec, A.g_rec};
-    for (int k = 0; k < 2; ++k) {
-      if (!host_rec[k]) continue;
-      if (done == ticks)
-        HIPCHK(hipMemcpyAsync(host_rec[k], dev_rec[k], n * stride * 4, hipMemcpyDeviceToHost, c->s));
-      else  // columns 0 .. done of every agent's row; the later ones stay as the caller left them
-        HIPCHK(hipMemcpy2DAsync(host_rec[k], stride * 4, dev_rec[k], stride * 4, ((size_t)done + 1) * 4, n,
-                                hipMemcpyDeviceToHost, c->s));
-    }
+    for (int k = 0; k < 2; ++k)  // columns 0 .. done
+      if (host_rec[k]) TRY(download_columns(c, host_rec[k], dev_rec[k], n, (size_t)done + 1, stride, 4));
     HIPCHK(hipStreamSynchronize(c->s));
     std::memcpy(v, c->h_fleet, n * 4ull);
     std::memcpy(g, c->h_fleet + n, n * 4ull);
@@ -474,16 +482,17 @@ static int fleet_run_impl(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n, uint
   TRY(ensure_tables(c, goals, true));
   FleetLists S;
   uint32_t* extra = nullptr;
-  TRY(fleet_lists_setup(c, n, radius, &S, fleet_apply_words(n), &extra));
+  const FleetApplyLayout L = fleet_apply_layout(n, nb_scan_blocks(n));
+  TRY(fleet_lists_setup(c, n, radius, &S, L.total, &extra));
   FleetApplyArgs A{};
-  fleet_apply_layout(&A, extra, n);
+  fleet_apply_state(&A, extra, L, n);
   A.v = S.v;
   A.g = S.g;
-  const size_t stride = (size_t)ticks + 1;
   if (v_rec || g_rec) {
-    TRY(grow_synced(c, c->d_fleet[2], ((v_rec ? 1 : 0) + (g_rec ? 1 : 0)) * (size_t)n * stride));
-    A.v_rec = v_rec ? c->d_fleet[2] : nullptr;
-    A.g_rec = g_rec ? c->d_fleet[2] + (v_rec ? (size_t)n * stride : 0) : nullptr;
+    const FleetRunRecLayout R = fleet_run_rec_layout((size_t)n * ((size_t)ticks + 1), v_rec != nullptr, g_rec != nullptr);
+    TRY(grow_synced(c, c->d_fleet[2], R.total));
+    A.v_rec = v_rec ? c->d_fleet[2] + R.v_rec : nullptr;
+    A.g_rec = g_rec ? c->d_fleet[2] + R.g_rec : nullptr;
     A.rec_stride = ticks + 1;
   }
   std::memcpy(c->h_fleet, v, n * 4ull);
@@ -556,12 +565,6 @@ int tsw_fleet_run(tsw_ctx* c, uint32_t* v, uint32_t* g, uint32_t n, uint32_t rad
 
 // ---- K5c: a MAPD run on the lock-step tick (tsw_fleet_mapd.hip around the K5 / K5b pipeline) ----------
 
-// words of the MAPD state behind n agents and m tasks: st (n) and the counter words, cleared together;
-// tk (n); the idle flags (n + 1) and their scan's block sums; pick | dlv (2 m)
-static size_t fleet_mapd_words(uint32_t n, uint32_t m) {
-  return 3 * (size_t)n + MAPD_WORDS + 1 + nb_scan_blocks(n) + 2 * (size_t)m;
-}
-
 static int fleet_mapd_impl(tsw_ctx* c, const std::vector<uint32_t>& vcell, const std::vector<uint32_t>& pick,
                            const std::vector<uint32_t>& dlv, uint32_t radius, uint32_t max_t, tsw_rec* out,
                            uint32_t* goal_out, uint32_t* task_out, uint32_t* out_T, uint32_t* stalled) {
@@ -578,33 +581,38 @@ static int fleet_mapd_impl(tsw_ctx* c, const std::vector<uint32_t>& vcell, const
   }
   FleetLists S;
   uint32_t* extra = nullptr;
-  TRY(fleet_lists_setup(c, n, radius, &S, fleet_apply_words(n) + fleet_mapd_words(n, m), &extra));
+  // behind the count pass: the apply state, and behind that the MAPD state
+  const FleetApplyLayout L = fleet_apply_layout(n, nb_scan_blocks(n));
+  const FleetMapdLayout ML = fleet_mapd_layout(n, m, MAPD_WORDS, nb_scan_blocks(n));
+  TRY(fleet_lists_setup(c, n, radius, &S, L.total + ML.total, &extra));
   TRY(fleet_hgrow(c, 2 * (size_t)n + 2 * (size_t)m + 4));
   FleetApplyArgs A{};
-  fleet_apply_layout(&A, extra, n);
+  fleet_apply_state(&A, extra, L, n);
   A.v = S.v;
   A.g = S.g;
+  uint32_t* const mapd = extra + L.total;
   FleetMapdArgs M{};
   M.n = n;
   M.m = m;
   M.W = c->G.W;
   M.v = S.v;
   M.g = S.g;
-  M.st = extra + fleet_apply_words(n);
-  M.words = M.st + n;
-  M.tk = M.words + MAPD_WORDS;
-  M.flag = M.tk + n;
-  M.bsum = M.flag + n + 1;
-  uint32_t* d_pick = M.bsum + nb_scan_blocks(n);
+  M.st = mapd + ML.st;
+  M.words = mapd + ML.words;
+  M.tk = mapd + ML.tk;
+  M.flag = mapd + ML.flag;
+  M.bsum = mapd + ML.bsum;
+  uint32_t* d_pick = mapd + ML.pick;
   M.pick = d_pick;
-  M.dlv = d_pick + m;
+  M.dlv = mapd + ML.dlv;
   M.tick_changed = A.changed;
-  // the records: tsw_rec (8 bytes) first, so that its columns are 8-byte aligned
-  const size_t stride = (size_t)max_t + 1, cols_words = (size_t)n * stride;
-  TRY(grow_synced(c, c->d_fleet[2], (2 + (goal_out ? 1 : 0) + (task_out ? 1 : 0)) * cols_words));
-  M.rec = reinterpret_cast<unsigned long long*>(c->d_fleet[2].p);
-  M.g_rec = goal_out ? c->d_fleet[2] + 2 * cols_words : nullptr;
-  M.t_rec = task_out ? c->d_fleet[2] + (goal_out ? 3 : 2) * cols_words : nullptr;
+  const size_t stride = (size_t)max_t + 1;
+  const FleetMapdRecLayout R = fleet_mapd_rec_layout((size_t)n * stride, goal_out != nullptr, task_out != nullptr);
+  TRY(grow_synced(c, c->d_fleet[2], R.total));
+  uint32_t* const dr = c->d_fleet[2];
+  M.rec = reinterpret_cast<unsigned long long*>(dr + R.rec);
+  M.g_rec = goal_out ? dr + R.g_rec : nullptr;
+  M.t_rec = task_out ? dr + R.t_rec : nullptr;
   M.rec_stride = max_t + 1;
   // v | g (= v: an idle agent's goal is its own cell), and pick | dlv, through the staging buffer
   uint32_t* h = c->h_fleet;
@@ -695,14 +703,8 @@ static int fleet_mapd_impl(tsw_ctx* c, const std::vector<uint32_t>& vcell, const
       const void* dev;
       size_t elem;
     } recs[3] = {{out, M.rec, 8}, {goal_out, M.g_rec, 4}, {task_out, M.t_rec, 4}};
-    for (const auto& r : recs) {
-      if (!r.host) continue;
-      if (cols == stride)
-        HIPCHK(hipMemcpyAsync(r.host, r.dev, cols_words * r.elem, hipMemcpyDeviceToHost, c->s));
-      else
-        HIPCHK(hipMemcpy2DAsync(r.host, stride * r.elem, r.dev, stride * r.elem, (size_t)cols * r.elem, n,
-                                hipMemcpyDeviceToHost, c->s));
-    }
+    for (const auto& r : recs)
+      if (r.host) TRY(download_columns(c, r.host, r.dev, n, cols, stride, r.elem));
     HIPCHK(hipStreamSynchronize(c->s));
     return TSW_OK;
   };

@@ -4,20 +4,9 @@
 // memory, and the prefix sum over the path lengths. The call reads the context's grid and nothing else of it:
 // the table store, the queues and the stats stay as they were. Host code only.
 #include "tsw_ctx.h"
+#include "tsw_layout.h"
 #include "tsw_place.h"
 #include "tsw_st_astar.h"
-
-// scratch that does not fit is TSW_ENOMEM here, not TSW_EHIP (grow_synced's code)
-template <class T>
-static int st_grow(tsw_ctx* c, DevBuf<T>& b, size_t need, const char* what) {
-  if (b.holds(need)) return TSW_OK;
-  HIPCHK(hipStreamSynchronize(c->s));
-  if (hipError_t e = b.grow(need); e != hipSuccess) {
-    (void)hipGetLastError();  // the failed allocation is reported by the code, not left pending
-    RET(e == hipErrorOutOfMemory ? TSW_ENOMEM : TSW_EHIP, std::string("space-time A* scratch (") + what + "): " + hipGetErrorString(e));
-  }
-  return TSW_OK;
-}
 
 // the scratch of a call stays below this and below half of the free memory
 static constexpr size_t ST_SCRATCH_MAX = (size_t)16 << 30;
@@ -70,7 +59,7 @@ int tsw_astar_reserved(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, 
     RET(TSW_ENOMEM, "space-time A*: the reservation set does not fit host memory (or holds more than 2^30 keys)");
   }
   if (!R.set.empty()) {
-    TRY(st_grow(c, c->d_st_res, R.set.size(), "reservations"));
+    TRY(scratch_grow(c, c->d_st_res, R.set.size(), "space-time A*", "reservations"));
     HIPCHK(hipMemcpyAsync(c->d_st_res, R.set.data(), R.set.size() * 8, hipMemcpyHostToDevice, c->s));
     HIPCHK(hipStreamSynchronize(c->s));
   }
@@ -92,22 +81,16 @@ int tsw_astar_reserved(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, 
   const uint32_t nslots = (uint32_t)std::min<uint64_t>(std::min<uint32_t>(k, waves), std::max<uint64_t>(budget / 4u * 3u / per_wave, 1u));
   size_t seg_budget = std::min<size_t>((budget - (size_t)nslots * per_wave) / 4u, ST_SEG_WORDS_MAX);
   if (c->tun.st_seg_words) seg_budget = std::min<size_t>(seg_budget, c->tun.st_seg_words);
-  TRY(st_grow(c, c->d_st_heap, (size_t)nslots * eff, "overflow heaps"));
+  TRY(scratch_grow(c, c->d_st_heap, (size_t)nslots * eff, "space-time A*", "overflow heaps"));
   const bool regrown = !c->d_st_vis.holds((size_t)nslots * vwords);
-  TRY(st_grow(c, c->d_st_vis, (size_t)nslots * vwords, "visited tables"));
+  TRY(scratch_grow(c, c->d_st_vis, (size_t)nslots * vwords, "space-time A*", "visited tables"));
   if (c->st_vis_words == 0) c->st_tag = std::max(c->tun.st_tag0, 1u);  // the context's first call
   if (regrown || c->st_vis_words != vwords) {
     c->st_vis_words = vwords;
     c->st_vis_wiped = 0;
   }
 
-  hipEvent_t ev[4] = {};
-  if (c->timing)
-    for (hipEvent_t& e : ev) e = ev_get(c);
-  auto done_events = [&]() {
-    if (c->timing)
-      for (hipEvent_t e : ev) c->pool.push_back(e);
-  };
+  PassTimer<4> pt(c);  // marks 0-1 around the search, 2-3 around the packing
   std::vector<uint32_t> h, all;  // all: the packed paths; they go to the caller once the total is known to fit
   std::vector<uint64_t> h_seg;
   uint64_t tot = 0;
@@ -136,15 +119,15 @@ int tsw_astar_reserved(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, 
         c->st_vis_wiped = nslots;
         if (wrap) c->st_tag = 1;
       }
-      // one block of words: start | goal | start_time | status | pops | len | path_off
-      TRY(st_grow(c, c->d_st_w, 7u * (size_t)kb, "queries and results"));
-      TRY(st_grow(c, c->d_st_segoff, (size_t)kb + 1u, "segment offsets"));
-      TRY(st_grow(c, c->d_st_seg, (size_t)h_seg.back(), "path segments"));
+      const StBatchLayout L = st_batch_layout(kb);
+      TRY(scratch_grow(c, c->d_st_w, L.total, "space-time A*", "queries and results"));
+      TRY(scratch_grow(c, c->d_st_segoff, (size_t)kb + 1u, "space-time A*", "segment offsets"));
+      TRY(scratch_grow(c, c->d_st_seg, (size_t)h_seg.back(), "space-time A*", "path segments"));
       uint32_t* const d = c->d_st_w.p;
-      h.resize(3u * (size_t)kb);
-      std::copy(start + b0, start + b1, h.begin());
-      std::copy(goal + b0, goal + b1, h.begin() + kb);
-      std::copy(start_time + b0, start_time + b1, h.begin() + 2u * (size_t)kb);
+      h.resize(L.status);  // start | goal | start_time go up together
+      std::copy(start + b0, start + b1, h.begin() + L.start);
+      std::copy(goal + b0, goal + b1, h.begin() + L.goal);
+      std::copy(start_time + b0, start_time + b1, h.begin() + L.start_time);
       HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->s));
       HIPCHK(hipMemcpyAsync(c->d_st_segoff, h_seg.data(), h_seg.size() * 8, hipMemcpyHostToDevice, c->s));
       StAstarArgs A{};
@@ -154,9 +137,9 @@ int tsw_astar_reserved(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, 
       A.Ww = c->G.Ww;
       A.freebits = c->G.freebits;
       A.k = kb;
-      A.start = d;
-      A.goal = d + kb;
-      A.start_time = d + 2u * (size_t)kb;
+      A.start = d + L.start;
+      A.goal = d + L.goal;
+      A.start_time = d + L.start_time;
       A.res = R.set.empty() ? nullptr : c->d_st_res.p;
       A.res_mask = R.mask;
       A.max_time = max_time;
@@ -171,18 +154,21 @@ int tsw_astar_reserved(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, 
       A.gheap = c->d_st_heap;
       A.seg_off = c->d_st_segoff;
       A.seg = c->d_st_seg;
-      A.status = d + 3u * (size_t)kb;
-      A.pops = d + 4u * (size_t)kb;
-      A.len = d + 5u * (size_t)kb;
+      A.status = d + L.status;
+      A.pops = d + L.pops;
+      A.len = d + L.len;
+      uint32_t* const d_boff = d + L.path_off;
       c->st_tag += iters;
-      if (c->timing) hipEventRecord(ev[0], c->s);
+      pt.mark(0);
       HIPCHK(launch_st_astar(A, cfg.lds, c->s));
-      if (c->timing) hipEventRecord(ev[1], c->s);
-      HIPCHK(hipMemcpyAsync(h.data(), A.status, 3u * (size_t)kb * 4, hipMemcpyDeviceToHost, c->s));
+      pt.mark(1);
+      // status | pops | len come back together
+      h.resize(L.path_off - L.status);
+      HIPCHK(hipMemcpyAsync(h.data(), A.status, h.size() * 4, hipMemcpyDeviceToHost, c->s));
       HIPCHK(hipStreamSynchronize(c->s));
       const uint32_t* const hs = h.data();
-      const uint32_t* const hp = hs + kb;
-      const uint32_t* const hl = hs + 2u * (size_t)kb;
+      const uint32_t* const hp = hs + (L.pops - L.status);
+      const uint32_t* const hl = hs + (L.len - L.status);
       std::vector<uint32_t> boff(kb);
       uint64_t btot = 0;
       for (uint32_t i = 0; i < kb; ++i) {
@@ -195,19 +181,18 @@ int tsw_astar_reserved(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, 
         tot += hl[i];
         if (tot > 0xFFFFFFFFull) RET(TSW_EOVERFLOW, "the paths hold more than 2^32 - 1 entries");
       }
-      float ms = 0.f;
-      if (c->timing && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->st_last[1] += ms;
+      c->st_last[1] += pt.elapsed(0);
       c->st_last[3] += 1.0;
       if (want_paths && tot <= path_cap && btot > 0) {
-        TRY(st_grow(c, c->d_st_path, (size_t)btot, "packed paths"));
-        HIPCHK(hipMemcpyAsync(d + 6u * (size_t)kb, boff.data(), (size_t)kb * 4, hipMemcpyHostToDevice, c->s));
-        if (c->timing) hipEventRecord(ev[2], c->s);
-        HIPCHK(launch_st_pack(kb, c->d_st_segoff, c->d_st_seg, d + 6u * (size_t)kb, A.len, c->d_st_path, c->s));
-        if (c->timing) hipEventRecord(ev[3], c->s);
+        TRY(scratch_grow(c, c->d_st_path, (size_t)btot, "space-time A*", "packed paths"));
+        HIPCHK(hipMemcpyAsync(d_boff, boff.data(), (size_t)kb * 4, hipMemcpyHostToDevice, c->s));
+        pt.mark(2);
+        HIPCHK(launch_st_pack(kb, c->d_st_segoff, c->d_st_seg, d_boff, A.len, c->d_st_path, c->s));
+        pt.mark(3);
         all.resize((size_t)tot);
         HIPCHK(hipMemcpyAsync(all.data() + (tot - btot), c->d_st_path, (size_t)btot * 4, hipMemcpyDeviceToHost, c->s));
         HIPCHK(hipStreamSynchronize(c->s));
-        if (c->timing && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) c->st_last[2] += ms;
+        c->st_last[2] += pt.elapsed(2);
       }
       b0 = b1;
     }
@@ -219,7 +204,6 @@ int tsw_astar_reserved(tsw_ctx* c, const uint32_t* start, const uint32_t* goal, 
     c->err = "space-time A*: host memory";
     rc = TSW_ENOMEM;
   }
-  done_events();
   c->st_last[4] = nslots;
   if (rc != TSW_OK) return rc;
   path_off[k] = (uint32_t)tot;

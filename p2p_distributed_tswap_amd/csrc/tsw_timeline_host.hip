@@ -5,20 +5,9 @@
 // context but its stream and scratch: the table store, the queues and the stats stay as they were.
 // Host code only.
 #include "tsw_ctx.h"
+#include "tsw_layout.h"
 #include "tsw_online.h"
 #include "tsw_timeline.h"
-
-// scratch that does not fit is TSW_ENOMEM here, not TSW_EHIP (grow_synced's code)
-template <class T>
-static int timeline_grow(tsw_ctx* c, DevBuf<T>& b, size_t need, const char* what) {
-  if (b.holds(need)) return TSW_OK;
-  HIPCHK(hipStreamSynchronize(c->s));
-  if (hipError_t e = b.grow(need); e != hipSuccess) {
-    (void)hipGetLastError();  // the failed allocation is reported by the code, not left pending
-    RET(e == hipErrorOutOfMemory ? TSW_ENOMEM : TSW_EHIP, std::string("timeline scratch (") + what + "): " + hipGetErrorString(e));
-  }
-  return TSW_OK;
-}
 
 extern "C" {
 
@@ -44,34 +33,28 @@ static int timeline_device(tsw_ctx* c, const unsigned long long* d_rec, uint32_t
                            const tsw_point* starts, const tsw_task* tasks, const uint32_t* release, uint32_t m,
                            uint32_t rule, tsw_timeline* sum, uint32_t* task) {
   const bool nearest = rule == TSW_TL_NEAREST;
-  // One block of words, in this order; the 8-byte parts start on even words:
-  //   q | w | task | colflag | vis | release | sorted | starts     come from the host image below
-  //   live                                                          pass B's own
-  const size_t mp = ((size_t)m + 1u) & ~(size_t)1u;  // m, even
-  const size_t o_q = 0, o_w = o_q + 2 * TL_NQ, o_task = o_w + TL_NW, o_flag = o_task + (size_t)m * TL_NTASK, o_vis = o_flag + T,
-               o_rel = o_vis + T, o_sorted = o_rel + mp, o_starts = o_sorted + 2 * (size_t)m,
-               o_live = o_starts + (nearest ? 2 * (size_t)n : 0), total = o_live + (nearest ? 2 * (size_t)m : 0);
-  static_assert((2 * TL_NQ + TL_NW) % 2 == 0, "task[] and what follows start on even words");
-  std::vector<uint32_t> h(o_live, 0u);
-  std::fill(h.begin() + o_q + 2 * TL_Q_FIRST0, h.begin() + o_q + 2 * TL_Q_BOUND + 2, 0xFFFFFFFFu);
-  h[o_w + TL_W_KIND] = h[o_w + TL_W_SMIN] = 0xFFFFFFFFu;
-  std::fill(h.begin() + o_task, h.begin() + o_flag, 0xFFFFFFFFu);
-  if (release) std::copy(release, release + m, h.begin() + o_rel);
+  // one block of words: everything before L.live comes from the host image below, live is pass B's own
+  const TimelineLayout L = timeline_layout(n, m, T, nearest, TL_NQ, TL_NW, TL_NTASK);
+  std::vector<uint32_t> h(L.live, 0u);
+  std::fill(h.begin() + L.q + 2 * TL_Q_FIRST0, h.begin() + L.q + 2 * TL_Q_BOUND + 2, 0xFFFFFFFFu);
+  h[L.w + TL_W_KIND] = h[L.w + TL_W_SMIN] = 0xFFFFFFFFu;
+  std::fill(h.begin() + L.task, h.begin() + L.colflag, 0xFFFFFFFFu);
+  if (release) std::copy(release, release + m, h.begin() + L.release);
   if (nearest) {
     const OnlineSchedule S = online_schedule(release, m, T - 1u);
     uint32_t j = 0;
     for (uint32_t t = 0; t < T; ++t) {  // vis[t]: tasks with release <= t, a prefix of the release order
       while (j < m && (!release || release[S.rel_order[j]] <= t)) ++j;
-      h[o_vis + t] = j;
+      h[L.vis + t] = j;
     }
     for (uint32_t q = 0; q < m; ++q) {
-      h[o_sorted + 2 * (size_t)q] = task_pxy(tasks[S.rel_order[q]]);
-      h[o_sorted + 2 * (size_t)q + 1] = S.rel_order[q];
+      h[L.sorted + 2 * (size_t)q] = task_pxy(tasks[S.rel_order[q]]);
+      h[L.sorted + 2 * (size_t)q + 1] = S.rel_order[q];
     }
-    std::memcpy(h.data() + o_starts, starts, (size_t)n * 8);  // tsw_point is two words
+    std::memcpy(h.data() + L.starts, starts, (size_t)n * 8);  // tsw_point is two words
   }
-  TRY(timeline_grow(c, c->d_tl_w, total, "tasks and columns"));
-  TRY(timeline_grow(c, c->d_tl_ev, (size_t)T * n, "events"));
+  TRY(scratch_grow(c, c->d_tl_w, L.total, "timeline", "tasks and columns"));
+  TRY(scratch_grow(c, c->d_tl_ev, (size_t)T * n, "timeline", "events"));
   uint32_t* const d = c->d_tl_w.p;
   TimelineArgs A{};
   A.n = n;
@@ -80,44 +63,33 @@ static int timeline_device(tsw_ctx* c, const unsigned long long* d_rec, uint32_t
   A.rule = rule;
   A.stride = stride;
   A.rec = d_rec;
-  A.starts = nearest ? reinterpret_cast<const uint2*>(d + o_starts) : nullptr;  // the allocation is 8-byte aligned
-  A.release = release ? d + o_rel : nullptr;
-  A.vis = nearest ? d + o_vis : nullptr;
-  A.sorted = nearest ? reinterpret_cast<const uint2*>(d + o_sorted) : nullptr;
-  A.live = nearest ? reinterpret_cast<uint2*>(d + o_live) : nullptr;
+  A.starts = nearest ? reinterpret_cast<const uint2*>(d + L.starts) : nullptr;
+  A.release = release ? d + L.release : nullptr;
+  A.vis = nearest ? d + L.vis : nullptr;
+  A.sorted = nearest ? reinterpret_cast<const uint2*>(d + L.sorted) : nullptr;
+  A.live = nearest ? reinterpret_cast<uint2*>(d + L.live) : nullptr;
   A.lds_cap = nearest ? tl_lds_candidates(m, c->max_lds) : 0u;
   A.ev = c->d_tl_ev;
-  A.colflag = d + o_flag;
-  A.q = reinterpret_cast<unsigned long long*>(d + o_q);
-  A.w = d + o_w;
-  A.task = d + o_task;
+  A.colflag = d + L.colflag;
+  A.q = reinterpret_cast<unsigned long long*>(d + L.q);
+  A.w = d + L.w;
+  A.task = d + L.task;
   HIPCHK(hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->s));
-  hipEvent_t ev[4] = {};
-  if (c->timing)
-    for (hipEvent_t& e : ev) e = ev_get(c);
-  auto mark = [&](int k) {
-    if (c->timing) hipEventRecord(ev[k], c->s);
-  };
-  mark(0);
+  PassTimer<4> pt(c);
+  pt.mark(0);
   HIPCHK(launch_timeline_events(A, c->s));
-  mark(1);
+  pt.mark(1);
   HIPCHK(launch_timeline_replay(A, c->s));
-  mark(2);
+  pt.mark(2);
   HIPCHK(launch_timeline_attach(A, c->s));
-  mark(3);
+  pt.mark(3);
   // q | w | task come down together
-  HIPCHK(hipMemcpyAsync(h.data(), d, o_flag * 4, hipMemcpyDeviceToHost, c->s));
+  HIPCHK(hipMemcpyAsync(h.data(), d, L.colflag * 4, hipMemcpyDeviceToHost, c->s));
   HIPCHK(hipStreamSynchronize(c->s));
-  const uint32_t* w = h.data() + o_w;
+  const uint32_t* w = h.data() + L.w;
   unsigned long long q[TL_NQ];
-  std::memcpy(q, h.data() + o_q, sizeof q);
-  for (int k = 0; k < 3; ++k) {
-    float ms = 0.f;
-    if (c->timing) hipEventElapsedTime(&ms, ev[k], ev[k + 1]);
-    c->tl_last[k] = ms;
-  }
-  if (c->timing)
-    for (hipEvent_t e : ev) c->pool.push_back(e);
+  std::memcpy(q, h.data() + L.q, sizeof q);
+  for (int k = 0; k < 3; ++k) c->tl_last[k] = pt.elapsed(k);
   c->tl_last[3] = w[TL_W_ASSIGNED];
   c->tl_last[4] = (double)((unsigned long long)w[TL_W_SCANNED_HI] << 32 | w[TL_W_SCANNED_LO]);
 
@@ -136,7 +108,7 @@ static int timeline_device(tsw_ctx* c, const unsigned long long* d_rec, uint32_t
   sum->bad_kind = w[TL_W_KIND];
   sum->bad_t = sum->consistent ? 0xFFFFFFFFu : (uint32_t)(q[TL_Q_BOUND] >> 32);
   sum->bad_agent = sum->consistent ? 0xFFFFFFFFu : (uint32_t)q[TL_Q_BOUND];
-  if (task) std::memcpy(task, h.data() + o_task, (size_t)m * TL_NTASK * 4);
+  if (task) std::memcpy(task, h.data() + L.task, (size_t)m * TL_NTASK * 4);
   return TSW_OK;
 }
 
@@ -180,11 +152,7 @@ int tsw_task_timeline(tsw_ctx* c, const tsw_rec* rec, uint32_t n, uint32_t T, ui
   if (empty) return TSW_OK;
   TRY(set_device(c));
   // columns 0 .. T - 1 of every row go up, packed, into the audit's record buffer
-  TRY(timeline_grow(c, c->d_aud_rec, (size_t)n * T, "records"));
-  if (stride == T)
-    HIPCHK(hipMemcpyAsync(c->d_aud_rec, rec, (size_t)n * T * 8, hipMemcpyHostToDevice, c->s));
-  else
-    HIPCHK(hipMemcpy2DAsync(c->d_aud_rec, (size_t)T * 8, rec, (size_t)stride * 8, (size_t)T * 8, n, hipMemcpyHostToDevice, c->s));
+  TRY(upload_records(c, rec, n, T, stride, "timeline"));
   return timeline_device(c, c->d_aud_rec, n, T, T, starts, tasks, release, m, rule, sum, task);
 }
 
